@@ -14,11 +14,20 @@ resident in HBM before the timed region:
         forward (batch-stat BatchReNorm, dropout) + loss + backward; every `sub_batch`-th step also
         all-reduces the flat gradient over RCCL (N>1) and applies clip+Adam -- BASELINE.json config 3/4.
   --mode infer: ICVL S=2 F=128 J=16 B=40 forward(eval) + vote -> xyz -- BASELINE.json config 2.
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel,
-HIP-event timed in a separate profiled pass over the same workload), `cpu_baseline` (the CPU
-oracle restatement timed on the host cores, rank 0 / N=1 only) and, in train mode, `forward_vote`: the
-other north-star figure (ICVL forward(eval)+vote crops/s, same N, same process) -- `metric`/`value`
-stay the fwd+bwd headline.
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times
+the K steps and prints the headline (`metric`, `value`, `unit`, `ms_per_step`, ...).  With --full it also
+measures, after the timed steps: `roofline` (dominant kernel, HIP-event timed in a separate profiled pass
+over the same workload; --detail asks for that pass on its own), `cpu_baseline` (the CPU oracle
+restatement timed on the host cores, rank 0 / N=1 only), in train mode `forward_vote`: the other
+north-star figure (ICVL forward(eval)+vote crops/s, same N, same process), and in infer mode with
+replicas `config.single_replica` (the same batches on one engine) -- `metric`/`value` stay the headline.
+Without --full these fields are null; --no-profile / --no-cpu-baseline / --no-forward-vote drop single
+legs from a --full run.
+
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (rank 0):
+train mode `losses.npy` (the loss terms the last step returned) and `params.npy` (every parameter after
+it, the engine's parameter order, flattened); infer mode `xyz.npy` (the joints of the last batch).  The
+inputs and weights are seeded, so the same arguments give the same inputs in every run.
 """
 from __future__ import annotations
 
@@ -67,11 +76,22 @@ def parse():
     ap.add_argument('--replicas', type=int, default=2,
                     help='forward(eval)+vote: inference replicas per GPU, consecutive batches alternate between them '
                          '(densereg_amd/serving.py; 1 = one engine, one stream)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run the roofline pass, the CPU baseline, the forward(eval)+vote leg (train '
+                         'mode) and the single-engine figure (infer mode with replicas); a plain run does only the headline')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='write what the timed path computed in its last step to DIR/<name>.npy (float32)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-profile', action='store_true')
     ap.add_argument('--no-forward-vote', action='store_true', help='train mode: skip the forward(eval)+vote leg')
-    ap.add_argument('--detail', default='', help='write a per-layer timing table (markdown) to this path')
-    return ap.parse_args()
+    ap.add_argument('--detail', default='', help='write a per-layer timing table (markdown) to this path (runs the profiled pass)')
+    args = ap.parse_args()
+    if not args.full:                                   # the legs past the headline are --full's (--detail asks for the profiled pass)
+        args.no_cpu_baseline = args.no_forward_vote = args.no_single = True
+        args.no_profile = args.no_profile or not args.detail
+    else:
+        args.no_single = False
+    return args
 
 
 def cpu_baseline(mode, cfg_tuple, B, dataset):
@@ -149,6 +169,26 @@ def pmc_traffic(mode, kernel):
         prov['note'] = 'kernel sources changed since the PMC passes (or the passes are unstamped): traffic not quoted'
         return None, prov
     return e['read_bytes_per_launch'] + e['write_bytes_per_launch'], prov
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, last, train_eng):
+    """--dump-outputs: the last timed step's results as float32 .npy files.  `last` holds what that step returned (device
+    tensors, complete after the timed region's synchronize); `train_eng` (train mode) adds the parameters the step left behind.
+    An array that would take the files past DUMP_MAX_BYTES is written as a fixed, seeded sample of its elements (sorted)."""
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in last.items()}
+    if train_eng is not None and hasattr(train_eng, 'read_params'):
+        arrays['params'] = np.concatenate([a.ravel() for a in train_eng.read_params().values()]).astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    room = DUMP_MAX_BYTES - sum(a.nbytes for k, a in arrays.items() if k != 'params') - (1 << 16)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, np.float32)
+        if a.nbytes > room:
+            idx = np.unique(np.random.default_rng(12345).integers(0, a.size, room // 4))
+            a = a.ravel()[idx]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 # DR_BENCH_DRYRUN=1: the N > 1 HOST logic of this file without a GPU -- spawn_ranks, the launcher's environment, rank -> device
@@ -308,6 +348,7 @@ def main():
         m_dm, m_cfg, m_com = (torch.cat([x] * MG) for x in (d_dm, d_cfg, d_com))
         m_xyz = eng.new(B * MG, 3 * J)
     pending = [0]                                            # micro-steps handed in since the last window / flush
+    last = {}                                                # what the latest step handed back to its caller (--dump-outputs)
     live_pools = []
 
     # forward(eval)+vote throughput: `--replicas` engines with the same weights, each on its own stream, take the batches in turn
@@ -326,21 +367,25 @@ def main():
     def step(i):
         if mode == 'infer':
             if pool is not None:
-                pool.submit(d_dm, d_cfg, d_com, out=pool_out[i % len(pool_out)])
+                last['xyz'] = pool.submit(d_dm, d_cfg, d_com, out=pool_out[i % len(pool_out)])[0]
             else:
-                eng.infer(d_dm, d_cfg, d_com, out=xyz)
+                last['xyz'] = eng.infer(d_dm, d_cfg, d_com, out=xyz)
+        elif G > 1 and pending[0] == 0 and trainer.micro % G:
+            # a flush() left the trainer inside an accumulation window (W or K not a multiple of G): finish that window micro-step
+            # by micro-step, window_step only takes whole ones
+            last['losses'] = trainer.micro_step(d_dm, d_pose, d_cfg, d_com, seed=i)
         elif G > 1:                                          # every G-th micro-step launches the window they form
             pending[0] += 1
             if pending[0] == G:
-                trainer.window_step(w_dm, w_pose, w_cfg, w_com, seed=i)
+                last['losses'] = trainer.window_step(w_dm, w_pose, w_cfg, w_com, seed=i)
                 pending[0] = 0
         else:
-            trainer.micro_step(d_dm, d_pose, d_cfg, d_com, seed=i)
+            last['losses'] = trainer.micro_step(d_dm, d_pose, d_cfg, d_com, seed=i)
 
     def flush():
         """micro-steps that do not fill a window (K or W not a multiple of G) run one by one: exactly K steps are timed"""
         for _ in range(pending[0]):
-            trainer.micro_step(d_dm, d_pose, d_cfg, d_com, seed=0)
+            last['losses'] = trainer.micro_step(d_dm, d_pose, d_cfg, d_com, seed=0)
         pending[0] = 0
         for p in live_pools:                                   # a merged group still filling: launched, so exactly K batches are timed
             p.flush()
@@ -374,10 +419,13 @@ def main():
         return el
 
     dt = timed(step)
+    if args.dump_outputs and rank == 0:                      # before any other leg runs the path again
+        dump_outputs(args.dump_outputs, last, eng if mode == 'train' else None)
     single = None
-    if pool is not None:                                     # the same workload on ONE engine / stream
-        sdt = timed(lambda i: eng.infer(d_dm, d_cfg, d_com, out=xyz))
-        single = {'value': B * world * args.steps / sdt, 'ms_per_step': sdt / args.steps * 1e3}
+    if pool is not None:
+        if not args.no_single:                               # the same workload on ONE engine / stream
+            sdt = timed(lambda i: eng.infer(d_dm, d_cfg, d_com, out=xyz))
+            single = {'value': B * world * args.steps / sdt, 'ms_per_step': sdt / args.steps * 1e3}
         pool.close()
         live_pools.remove(pool)
         pool = None

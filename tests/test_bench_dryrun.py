@@ -49,3 +49,19 @@ def test_rank_count_that_differs_from_gpus_is_refused():
     r = _run(['--gpus', '2', '--steps', '1'], {'WORLD_SIZE': '1', 'RANK': '0', 'LOCAL_RANK': '0'})
     assert r.returncode == 2 and 'they must agree' in r.stderr
     assert r.stdout.strip() == ''
+
+
+def test_unaligned_warmup_exact_steps_and_dump_outputs(tmp_path):
+    """A warm-up that ends inside an accumulation window (W = 3, G = 5) is finished micro-step by micro-step before the next window:
+    exactly K steps are timed, ``--dump-outputs`` writes the last step's loss terms as float32, and a plain run (no ``--full``) leaves
+    the legs past the headline null."""
+    import numpy as np
+    out = tmp_path / 'dump'
+    r = _run(['--gpus', '2', '--steps', '12', '--warmup', '3', '--dump-outputs', str(out)], {})
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.strip())
+    assert d['steps'] == 12 and d['warmup'] == 3 and d['ms_per_step'] > 0
+    assert d['config']['checked_all_reduces'] == 3                        # 15 micro-steps = 3 optimizer steps
+    assert d['roofline'] is None and d['cpu_baseline'] is None and d['forward_vote'] is None
+    losses = np.load(out / 'losses.npy')
+    assert losses.dtype == np.float32 and losses.shape[-1] == 4
