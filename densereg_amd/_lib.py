@@ -24,6 +24,18 @@ class DrConfig(C.Structure):
                 ('kernel_size', C.c_int32), ('max_batch', C.c_int32), ('device', C.c_int32), ('training', C.c_int32)]
 
 
+class DrVoteReport(C.Structure):
+    """include/densereg.h: struct dr_vote_report -- device addresses, None / 0 = member not wanted."""
+    _fields_ = [(n, C.c_void_p) for n in ('xyz_norm_dev', 'uvd_dev', 'can_idx_dev', 'can_score_dev', 'can_pts_dev',
+                                           'ori_pts_dev', 'can_weight_dev', 'mass_dev', 'hm_peak_dev')]
+
+
+# member of DrVoteReport without its _dev suffix -> (trailing shape after (B, J), is_int32)
+VOTE_REPORT_FIELDS = {'xyz_norm': ((3,), False), 'uvd': ((3,), False), 'can_idx': ((5,), True), 'can_score': ((5,), False),
+                      'can_pts': ((5, 3), False), 'ori_pts': ((5, 3), False), 'can_weight': ((5,), False), 'mass': ((), False),
+                      'hm_peak': ((3,), False)}
+
+
 class KernelStat(C.Structure):
     _fields_ = [('name', C.c_char * 64), ('launches', C.c_int64), ('total_ms', C.c_double), ('flops', C.c_double),
                 ('bytes', C.c_double)]
@@ -68,6 +80,8 @@ SIGNATURES = {
     'dr_read_maps': (_i, [_vp, _i, _i, _fp, _fp, _fp, _vp]),
     'dr_vote': (_i, [_vp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp]),
     'dr_infer': (_i, [_vp, _i, _fp, _fp, _fp, _fp, _vp]),
+    'dr_vote_report': (_i, [_vp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.POINTER(DrVoteReport), _vp]),
+    'dr_infer_report': (_i, [_vp, _i, _fp, _fp, _fp, _fp, C.POINTER(DrVoteReport), _vp]),
     'dr_forward_train': (_i, [_vp, _i, _fp, _i, _vp, C.c_uint64, _vp]),
     'dr_loss': (_i, [_vp, _i, _fp, _fp, _fp, _fp, _fp, _vp]),
     'dr_backward': (_i, [_vp, _i, _vp]),

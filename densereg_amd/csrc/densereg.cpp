@@ -1568,18 +1568,50 @@ static void copy_out(dr_handle* h, const Tensor* t, int B, float* dst, hipStream
 }
 
 static int vote_impl(dr_handle* h, int B, View hm, View hm3, View um, const float* tiny, const float* cfg, const float* com,
-                     float* xyz, hipStream_t s) {
+                     float* xyz, hipStream_t s, const struct dr_vote_report* report = nullptr) {
     VoteParams vp{};
     vp.hm = hm; vp.hm3 = hm3; vp.um = um; vp.tiny = tiny; vp.cfg = cfg; vp.com = com; vp.xyz_mm = xyz; vp.xyz_norm = nullptr;
     vp.B = B; vp.h = h->map_hw; vp.w = h->map_hw; vp.J = h->cfg.num_jnt;
     const int npix = vp.h * vp.w;
     if (npix > kVoteMaxPix) DR_FAIL(h, DR_E_UNSUPPORTED, "vote: map of %d px exceeds the LDS plan", npix);
-    {
+    if (report) {
+        // vote_report_kernel: the same launch geometry and LDS plan; the caller's struct is copied into the launch arguments here.
+        // Accounted under the vote's kernel id (one more read of hm when the peak is wanted, up to 220 B per joint written).
+        vp.xyz_norm = report->xyz_norm_dev;
+        VoteReport vr{};
+        vr.uvd = report->uvd_dev; vr.can_idx = report->can_idx_dev; vr.can_score = report->can_score_dev;
+        vr.can_pts = report->can_pts_dev; vr.ori_pts = report->ori_pts_dev; vr.can_weight = report->can_weight_dev;
+        vr.mass = report->mass_dev; vr.hm_peak = report->hm_peak_dev;
+        ProfScope ps(h, s, KID_VOTE, 0.0, (double)B * ((5.0 * vp.J + 1.0 + (vr.hm_peak ? vp.J : 0)) * npix * 4.0 + 12.0 * vp.J));
+        DR_LAUNCH(vote_report_kernel, dim3(B, dr_ceil_div(vp.J, kVoteJC)), dim3(256), (size_t)kVoteJC * npix * sizeof(float), s, vp, vr);
+    } else {
         ProfScope ps(h, s, KID_VOTE, 0.0, (double)B * ((5.0 * vp.J + 1.0) * npix * 4.0 + 12.0 * vp.J));
         DR_LAUNCH(vote_kernel, dim3(B, dr_ceil_div(vp.J, kVoteJC)), dim3(256), (size_t)kVoteJC * npix * sizeof(float), s, vp);
     }
     DR_CHECK_LAUNCH(h);
     return DR_OK;
+}
+
+// dr_vote / dr_vote_report: the vote on caller-provided maps, with or without a report (one body, so the two cannot drift apart)
+static int vote_on_maps(dr_handle* h, int B, const float* hm, const float* hm3, const float* um, const float* dm, const float* cfg,
+                        const float* com, float* xyz, const struct dr_vote_report* report, hipStream_t s) {
+    if (B < 1 || B > h->cfg.max_batch) DR_FAIL(h, DR_E_INVALID, "batch %d outside [1, max_batch=%d]", B, h->cfg.max_batch);
+    DR_ENTER(h);
+    const int J = h->cfg.num_jnt, mh = h->map_hw;
+    DR_LAUNCH(uvd_kernel, dim3(grid_for((long)B * mh * mh)), dim3(256), 0, s, dm, B, h->cfg.in_hw, h->tiny_ext, (float*)nullptr,
+              0, 0, (float*)nullptr, 0, 0);
+    return vote_impl(h, B, View{(float*)hm, J, 0, J}, View{(float*)hm3, J, 0, J}, View{(float*)um, 3 * J, 0, 3 * J},
+                     h->tiny_ext, cfg, com, xyz, s, report);
+}
+
+// dr_infer / dr_infer_report: forward(eval) + vote on the last stack's maps in place, with or without a report
+static int infer_launches(dr_handle* h, int B, const float* dm, const float* cfg, const float* com, float* xyz,
+                          const struct dr_vote_report* report, hipStream_t s) {
+    int rc = forward_eval_impl(h, B, dm, s);
+    if (rc) return rc;
+    const int S = h->cfg.num_stack - 1;
+    TView a{h->hm[S], 0, h->hm[S]->C}, b{h->hm3[S], 0, h->hm3[S]->C}, c{h->um[S], 0, h->um[S]->C};
+    return vote_impl(h, B, a.fwd(), b.fwd(), c.fwd(), h->tiny, cfg, com, xyz, s, report);
 }
 
 extern "C" {
@@ -1609,25 +1641,30 @@ int dr_read_maps(dr_handle* h, int B, int stack, float* hm, float* hm3, float* u
 int dr_vote(dr_handle* h, int B, const float* hm, const float* hm3, const float* um, const float* dm, const float* cfg,
             const float* com, float* xyz, dr_stream stream) {
     if (!h || !hm || !hm3 || !um || !dm || !cfg || !com || !xyz) return DR_E_INVALID;
-    if (B < 1 || B > h->cfg.max_batch) DR_FAIL(h, DR_E_INVALID, "batch %d outside [1, max_batch=%d]", B, h->cfg.max_batch);
-    DR_ENTER(h);
-    hipStream_t s = (hipStream_t)stream;
-    const int J = h->cfg.num_jnt, mh = h->map_hw;
-    DR_LAUNCH(uvd_kernel, dim3(grid_for((long)B * mh * mh)), dim3(256), 0, s, dm, B, h->cfg.in_hw, h->tiny_ext, (float*)nullptr,
-              0, 0, (float*)nullptr, 0, 0);
-    return vote_impl(h, B, View{(float*)hm, J, 0, J}, View{(float*)hm3, J, 0, J}, View{(float*)um, 3 * J, 0, 3 * J},
-                     h->tiny_ext, cfg, com, xyz, s);
+    return vote_on_maps(h, B, hm, hm3, um, dm, cfg, com, xyz, nullptr, (hipStream_t)stream);
 }
 
 int dr_infer(dr_handle* h, int B, const float* dm, const float* cfg, const float* com, float* xyz, dr_stream stream) {
     if (!h || !dm || !cfg || !com || !xyz) return DR_E_INVALID;
-    return run_with_graph(h, 1, B, {dm, cfg, com, xyz}, (hipStream_t)stream, [&](hipStream_t s) {
-        int rc = forward_eval_impl(h, B, dm, s);
-        if (rc) return rc;
-        const int S = h->cfg.num_stack - 1;
-        TView a{h->hm[S], 0, h->hm[S]->C}, b{h->hm3[S], 0, h->hm3[S]->C}, c{h->um[S], 0, h->um[S]->C};
-        return vote_impl(h, B, a.fwd(), b.fwd(), c.fwd(), h->tiny, cfg, com, xyz, s);
-    });
+    return run_with_graph(h, 1, B, {dm, cfg, com, xyz}, (hipStream_t)stream,
+                          [&](hipStream_t s) { return infer_launches(h, B, dm, cfg, com, xyz, nullptr, s); });
+}
+
+int dr_vote_report(dr_handle* h, int B, const float* hm, const float* hm3, const float* um, const float* dm, const float* cfg,
+                   const float* com, float* xyz, const struct dr_vote_report* report, dr_stream stream) {
+    if (!h || !hm || !hm3 || !um || !dm || !cfg || !com || !xyz) return DR_E_INVALID;
+    if (!report) DR_FAIL(h, DR_E_INVALID, "dr_vote_report: report is NULL (dr_vote is the entry point without one)");
+    return vote_on_maps(h, B, hm, hm3, um, dm, cfg, com, xyz, report, (hipStream_t)stream);
+}
+
+// Launches directly, never through run_with_graph: a graph recorded here would bake the nine report pointers into its
+// launches, and a replay keyed on anything less would write into another call's buffers.  The forward's launches are the ones
+// dr_infer makes; only the last one differs (vote_report_kernel).
+int dr_infer_report(dr_handle* h, int B, const float* dm, const float* cfg, const float* com, float* xyz,
+                    const struct dr_vote_report* report, dr_stream stream) {
+    if (!h || !dm || !cfg || !com || !xyz) return DR_E_INVALID;
+    if (!report) DR_FAIL(h, DR_E_INVALID, "dr_infer_report: report is NULL (dr_infer is the entry point without one)");
+    return infer_launches(h, B, dm, cfg, com, xyz, report, (hipStream_t)stream);
 }
 
 int dr_read_activation(dr_handle* h, const char* scope, int B, float* host, size_t count) {

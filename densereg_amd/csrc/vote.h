@@ -18,6 +18,10 @@
 // here differed from numpy's by an ulp, and ten mean-shift iterations between two candidate clusters amplified that ulp to 0.3 mm
 // on a handful of knife-edge joints (rounds 1-5).  Documented choices: an out-of-range re-projected
 // pixel contributes weight 0 (TF-GPU gather_nd), and a zero/non-finite kernel mass keeps the centre.
+//
+// vote_report_kernel is the same body (vote_body<true>) that also stores what the reference's test graph exposes as its "interface to
+// fetch output" (:464-471, 521-526, 781-784) -- uvd joints, candidates, their point-cloud positions, weights, the heat-map-only peak --
+// and the kernel mass at the final centre, each behind a nullable pointer (struct VoteReport).  Same geometry, LDS plan and xyz bits.
 #pragma once
 #include "dr_platform.h"
 #include "kernels_misc.h"
@@ -32,6 +36,19 @@ struct VoteParams {
     float* xyz_mm;               // (B,3J) out, millimetres
     float* xyz_norm;             // nullable (B,3J) normalised
     int B, h, w, J;
+};
+
+// What vote_report_kernel stores next to xyz_mm (dr_vote_report of include/densereg.h; xyz_norm_dev travels as
+// VoteParams::xyz_norm).  Every member is nullable = not wanted; all dense, row-major.
+struct VoteReport {
+    float* uvd;                  // (B,J,3)   joint in mm projected with the crop camera cfg[b]: self.uvd_pts (:467)
+    int* can_idx;                // (B,J,5)   map pixel of each candidate, tf.nn.top_k order
+    float* can_score;            // (B,J,5)   refined heat ((hm+1)*hm3)*mask at those pixels
+    float* can_pts;              // (B,J,5,3) candidates, normalised: self.can_pts
+    float* ori_pts;              // (B,J,5,3) point cloud at the same pixels, normalised: self.ori_pts
+    float* can_weight;           // (B,J,5)   raw hm at the re-projected pixel, 0 out of range
+    float* mass;                 // (B,J)     mean-shift kernel mass at the final centre (extension)
+    float* hm_peak;              // (B,J,3)   (u, v, value) of the first maximum of the raw hm[b,:,:,j]: _uvd_estimation_op (:788-814)
 };
 
 constexpr int kVoteJC = 4;         // joints per workgroup (= waves)
@@ -73,7 +90,10 @@ __device__ __forceinline__ void vote_argmax_first(float& v, int& idx) {
     }
 }
 
-__global__ __launch_bounds__(256) void vote_kernel(const VoteParams p) {
+// One body for both entry kernels.  REPORT = false is vote_kernel: `rep` is never touched and every report store / load below
+// is compiled out (if constexpr), so the plain kernel keeps its instructions and its bits.
+template <bool REPORT>
+__device__ __forceinline__ void vote_body(const VoteParams& p, const VoteReport& rep) {
 #pragma clang fp contract(off)
     DR_DYN_SMEM(smem_raw);
     float* ref = reinterpret_cast<float*>(smem_raw);      // [kVoteJC][npix]
@@ -130,6 +150,28 @@ __global__ __launch_bounds__(256) void vote_kernel(const VoteParams p) {
         sel[k] = bi;
     }
 
+    // ---- report: heat-map-only estimate, the first maximum of the RAW hm[b,:,:,j] (no depth mask) ---------------
+    // Wave-local and lane-strided over the joint's column of hm, which phase 1 has just pulled through L2.  Ties -> lowest
+    // row-major index (tf.where(...)[0], :808-811); NaN fails both comparisons and is never selected; nothing selected -> pixel 0.
+    if constexpr (REPORT) {
+        if (rep.hm_peak) {
+            const float* hj = p.hm.p + (long)b * npix * p.hm.cs + p.hm.coff + j;
+            float bv = -INFINITY;
+            int bi = 0x7fffffff;
+            for (int px = lane; px < npix; px += 64) {
+                const float v = hj[(long)px * p.hm.cs];
+                if (v > bv || (v == bv && px < bi)) { bv = v; bi = px; }
+            }
+            if (bi == 0x7fffffff) bv = -INFINITY;
+            vote_argmax_first(bv, bi);
+            if (bi == 0x7fffffff) bi = 0;
+            if (lane < 3) {
+                const float val = hj[(long)bi * p.hm.cs];
+                rep.hm_peak[((long)b * J + j) * 3 + lane] = lane == 0 ? (float)(bi % p.w) : (lane == 1 ? (float)(bi / p.w) : val);
+            }
+        }
+    }
+
     // ---- candidates + weights: lane i < 5 owns candidate i ------------------------------------
     const float* cfg = p.cfg + b * 6;
     const float cx0 = p.com[b * 3 + 0], cy0 = p.com[b * 3 + 1], cz0 = p.com[b * 3 + 2];
@@ -170,6 +212,16 @@ __global__ __launch_bounds__(256) void vote_kernel(const VoteParams p) {
             const int uu = (int)uf, vv = (int)vf;                                      // trunc toward 0
             const long mm = (long)b * npix + vv * p.w + uu;
             wt = p.hm.p[mm * p.hm.cs + p.hm.coff + j];
+        }
+        if constexpr (REPORT) {
+            if (lane < 5) {
+                const long o = ((long)b * J + j) * 5 + lane;
+                if (rep.can_idx) rep.can_idx[o] = px;
+                if (rep.can_score) rep.can_score[o] = rj[px];
+                if (rep.can_weight) rep.can_weight[o] = wt;
+                if (rep.can_pts) { rep.can_pts[3 * o + 0] = c0; rep.can_pts[3 * o + 1] = c1; rep.can_pts[3 * o + 2] = c2; }
+                if (rep.ori_pts) { rep.ori_pts[3 * o + 0] = X; rep.ori_pts[3 * o + 1] = Y; rep.ori_pts[3 * o + 2] = Z; }
+            }
         }
     }
     float cp[5][3], cw[5];
@@ -235,6 +287,35 @@ __global__ __launch_bounds__(256) void vote_kernel(const VoteParams p) {
         if (p.xyz_norm) p.xyz_norm[o] = cn;
         p.xyz_mm[o] = cn * 100.0f + cm;
     }
+    if constexpr (REPORT) {
+        // kernel mass at the final centre, once after the loop (or its early break): the reference's own kernel weight
+        if (rep.mass) {
+            float ss = 0.f;
+#pragma unroll
+            for (int i = 0; i < 5; ++i) {
+                const float d0 = cp[i][0] - ctr[0], d1 = cp[i][1] - ctr[1], d2 = cp[i][2] - ctr[2];
+                const float s = (d0 * d0 + d1 * d1) + d2 * d2;
+                ss = ss + vote_exp(inv_sigma * s) * cw[i];
+            }
+            if (lane == 0) rep.mass[(long)b * J + j] = ss;
+        }
+        // xyz2uvd_op with the crop's own camera, unscaled (data/util.py:20 _pro): u = (x*fx)/z + cx, v = (y*fy)/z + cy, d = z
+        if (rep.uvd && lane < 3) {
+            const float x = ctr[0] * 100.0f + cx0, y = ctr[1] * 100.0f + cy0, z = ctr[2] * 100.0f + cz0;
+            const float u = (x * cfg[0]) / z + cfg[2];
+            const float v = (y * cfg[1]) / z + cfg[3];
+            rep.uvd[((long)b * J + j) * 3 + lane] = lane == 0 ? u : (lane == 1 ? v : z);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void vote_kernel(const VoteParams p) {
+    vote_body<false>(p, VoteReport{});
+}
+
+// The same vote plus the report: same launch geometry, same LDS plan, same xyz_mm bits.
+__global__ __launch_bounds__(256) void vote_report_kernel(const VoteParams p, const VoteReport rep) {
+    vote_body<true>(p, rep);
 }
 
 }  // namespace dr

@@ -7,7 +7,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import sys
-from typing import Dict, Optional
+from typing import Dict, Iterable, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -27,6 +27,33 @@ def _f32(t: torch.Tensor) -> torch.Tensor:
     return t
 
 
+MAP_STRIDE = 4      # input side / map side for every accepted crop size (um_v1.py:109)
+
+
+class VoteReport(NamedTuple):
+    """What ``Engine.vote_report`` / ``infer_report`` fetch next to the joints (``struct dr_vote_report``): the reference's
+    "interface to fetch output" (hourglass_um_crop_tiny.py:464-471, 521-526, 781-784).  Members that were not asked for are ``None``."""
+    xyz_norm: Optional[torch.Tensor]        # (B,J,3)   normalised mean-shift centre
+    uvd: Optional[torch.Tensor]             # (B,J,3)   self.uvd_pts: the joints projected into the crop
+    can_idx: Optional[torch.Tensor]         # (B,J,5)   int32 map pixel of each candidate, top_k order
+    can_score: Optional[torch.Tensor]       # (B,J,5)   refined heat at those pixels
+    can_pts: Optional[torch.Tensor]         # (B,J,5,3) self.can_pts
+    ori_pts: Optional[torch.Tensor]         # (B,J,5,3) self.ori_pts
+    can_weight: Optional[torch.Tensor]      # (B,J,5)   _get_candidate_weights
+    mass: Optional[torch.Tensor]            # (B,J)     mean-shift kernel mass at the final centre (extension: a confidence)
+    hm_peak: Optional[torch.Tensor]         # (B,J,3)   (u, v, value) of the raw heat map's first maximum, map resolution
+
+    @property
+    def hm_uvd_pts(self) -> Optional[torch.Tensor]:
+        """self.hm_uvd_pts (:471), (B,3J): the heat-map peak at input resolution with d = 1 (the reference passes ds = ones).  With the
+        legacy bilinear resize every map pixel is an input pixel exactly, so the peak of the resized map is the map's peak scaled by
+        in_hw / map_hw = 4 (the network's maps are a quarter of the input side, um_v1.py:109)."""
+        if self.hm_peak is None:
+            return None
+        uv = self.hm_peak[..., :2] * float(MAP_STRIDE)
+        return torch.cat([uv, torch.ones_like(uv[..., :1])], dim=-1).reshape(uv.shape[0], -1)
+
+
 class Engine:
     """One engine per (process, device).  Mirrors the call sites of the reference:
 
@@ -34,6 +61,9 @@ class Engine:
     * ``vote`` / ``infer``                  <->  ``JointDetectionModel._xyz_estimation`` / ``.test``
     * ``loss`` / ``backward`` / ``apply_adam`` <-> ``.loss`` and the step of ``train_single_gpu.train``
     """
+
+    _holders = 0                # trainers bound to this engine (retain / release)
+    _close_pending = False      # close() was asked for while a holder was bound
 
     def __init__(self, num_stack=2, num_fea=128, num_jnt=16, in_hw=128, kernel_size=3, max_batch=40,
                  device: int = 0, training: bool = False, pipeline: Optional[int] = None):
@@ -62,7 +92,7 @@ class Engine:
                         raise
                     sys.stderr.write('densereg_amd: no memory for a second micro-step slot, running one micro-step at a time (%s)\n' % e)
         self.num_stack, self.num_fea, self.num_jnt, self.in_hw = num_stack, num_fea, num_jnt, in_hw
-        self.map_hw = in_hw // 4
+        self.map_hw = in_hw // MAP_STRIDE
         self.max_batch = max_batch
         self.training = training
         self.groups = 1
@@ -72,7 +102,24 @@ class Engine:
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def close(self):
+        """Destroy the native handle (weights, workspaces, streams).  While a holder is bound (``retain``: a
+        ``DataParallelTrainer`` keeps a zero-copy view of the flat gradient buffer and launches on this engine) the
+        handle stays alive and is destroyed when the last holder lets go: the holder's views never dangle and a
+        micro-step it still owes runs instead of failing on a destroyed handle."""
+        if self._holders > 0:
+            self._close_pending = True
+            return
         self.h.close()
+
+    def retain(self):
+        """A holder (an object that aliases this engine's device memory) binds itself; pair with ``release``."""
+        self._holders += 1
+
+    def release(self):
+        self._holders -= 1
+        if self._holders <= 0 and self._close_pending:
+            self._close_pending = False
+            self.h.close()
 
     def set_precision(self, precision: str):
         """'f32' (default) or 'bf16': matrix-core arithmetic of every k != 7 convolution of the handle (dr_set_precision) --
@@ -131,6 +178,35 @@ class Engine:
         xyz = out if out is not None else self.new(B, 3 * self.num_jnt)
         self.h.call('dr_infer', B, _p(dm_norm), _p(cfg), _p(com), _p(xyz), self._stream())
         return xyz
+
+    def _new_report(self, B: int, fields: Optional[Iterable[str]]):
+        """Buffers of the requested members (``None`` = all) and the C struct that names them; the rest stay NULL."""
+        want = tuple(_lib.VOTE_REPORT_FIELDS) if fields is None else tuple(fields)
+        unknown = [f for f in want if f not in _lib.VOTE_REPORT_FIELDS]
+        if unknown:
+            raise ValueError('unknown vote report member(s) %s; known: %s' % (unknown, ', '.join(_lib.VOTE_REPORT_FIELDS)))
+        bufs, c_rep = {}, _lib.DrVoteReport()
+        for name, (tail, is_int) in _lib.VOTE_REPORT_FIELDS.items():
+            bufs[name] = self.new(B, self.num_jnt, *tail, dtype=torch.int32 if is_int else torch.float32) if name in want else None
+            setattr(c_rep, name + '_dev', _p(bufs[name]))
+        return VoteReport(**bufs), c_rep
+
+    def vote_report(self, hm, hm3, um, dm_norm, cfg, com, fields: Optional[Iterable[str]] = None):
+        """``vote`` plus the report of the same launch (``dr_vote_report``): ``(xyz_mm, VoteReport)``.  ``fields`` names the
+        members to fetch (default: all); the others are ``None`` and cost nothing."""
+        B = dm_norm.shape[0]
+        xyz = self.new(B, 3 * self.num_jnt)
+        rep, c_rep = self._new_report(B, fields)
+        self.h.call('dr_vote_report', B, _p(hm), _p(hm3), _p(um), _p(dm_norm), _p(cfg), _p(com), _p(xyz), C.byref(c_rep), self._stream())
+        return xyz, rep
+
+    def infer_report(self, dm_norm, cfg, com, fields: Optional[Iterable[str]] = None):
+        """``infer`` plus the report (``dr_infer_report``): ``(xyz_mm, VoteReport)``."""
+        B = dm_norm.shape[0]
+        xyz = self.new(B, 3 * self.num_jnt)
+        rep, c_rep = self._new_report(B, fields)
+        self.h.call('dr_infer_report', B, _p(dm_norm), _p(cfg), _p(com), _p(xyz), C.byref(c_rep), self._stream())
+        return xyz, rep
 
     def read_activation(self, scope: str, B: int, shape) -> np.ndarray:
         torch.cuda.synchronize(self.device)

@@ -138,10 +138,16 @@ class JointDetectionModel(object):
         and ``unnorm_xyz_pose`` (:462) are inside the kernel.  Returns xyz in mm, (B, 3J)."""
         return self.engine.vote(hms, hm3s, ums, dms, cfgs, coms)
 
-    def test(self, dms, poses, cfgs, coms):
-        """(:442-462) depth (mm) -> xyz (mm)."""
+    def test(self, dms, poses, cfgs, coms, report=False):
+        """(:442-462) depth (mm) -> xyz (mm).  ``report=True`` also sets the reference's fetch interface (:521-526, :783-784):
+        ``self.uvd_pts`` (B,J,3), ``self.can_pts`` / ``self.ori_pts`` (B,J,5,3) and ``self.hm_uvd_pts`` (B,3J), written by the
+        vote's own launch."""
         normed = self.engine.norm_dm(dms, coms)
-        return self.engine.infer(normed, cfgs, coms)
+        if not report:
+            return self.engine.infer(normed, cfgs, coms)
+        xyz, rep = self.engine.infer_report(normed, cfgs, coms, fields=('uvd', 'can_pts', 'ori_pts', 'hm_peak'))
+        self.uvd_pts, self.can_pts, self.ori_pts, self.hm_uvd_pts = rep.uvd, rep.can_pts, rep.ori_pts, rep.hm_uvd_pts
+        return xyz
 
     def loss(self, dms, poses, cfgs, coms, seed=0):
         """(:323-371) one training micro-step's forward + loss; returns the 4 terms hm, hm3, um, reg."""

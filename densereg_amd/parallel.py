@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import math
 import os
+import weakref
 
 from .data.synthetic import DATASETS
 
@@ -93,6 +94,12 @@ class DataParallelTrainer:
         self.micro = 0
         self.global_step = 0                     # optimizer steps applied so far
         self.flat_grad = engine.flat_view('grad') if engine is not None else None
+        # flat_grad aliases the engine's gradient buffer: the engine outlives this trainer even if its owner closes it first
+        # (Engine.close then takes effect when the trainer is released)
+        retain, release = getattr(engine, 'retain', None), getattr(engine, 'release', None)
+        if retain is not None and release is not None:
+            retain()
+            weakref.finalize(self, release).atexit = False
         if engine is not None:
             # an optimizer step after EVERY micro-step leaves nothing to overlap and the second slot's bookkeeping only costs
             # (measured: 1867 against 2054 crops/s): one micro-step at a time then

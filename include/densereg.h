@@ -125,6 +125,42 @@ int dr_vote(dr_handle* h, int B, const float* hm_dev, const float* hm3_dev, cons
 int dr_infer(dr_handle* h, int B, const float* dm_norm_dev, const float* cfg_dev, const float* com_dev,
              float* xyz_mm_dev, dr_stream stream);
 
+/* ---- vote report --------------------------------------------------------------------------------- */
+/* What the reference's test graph exposes next to the joints as its "interface to fetch output"
+ * (hourglass_um_crop_tiny.py:464-471, 521-526, 781-784), written by the vote's own launch.  Device pointers; any
+ * member may be NULL = not wanted.  Dense, row-major, float32 unless noted; J = num_jnt, 5 = the candidates per
+ * joint (num_pt, :770).  The struct is read during the call: the caller may free it on return.  (A struct tag, not a
+ * typedef: the entry point below has the same name, and C keeps tags and functions apart.) */
+struct dr_vote_report {
+    float* xyz_norm_dev;    /* (B,J,3)   the mean-shift centre, normalised: _xyz_estimation's result (:775, :785) before
+                             *           unnorm_xyz_pose (:462) */
+    float* uvd_dev;         /* (B,J,3)   self.uvd_pts (:467, :522): xyz2uvd_op = _pro of data/util.py:20 on the joint in mm with the
+                             *           crop's camera cfg[b], unscaled: u = x*fx/z + cx, v = y*fy/z + cy, d = z */
+    int32_t* can_idx_dev;   /* (B,J,5)   int32: row-major map pixel of each candidate in tf.nn.top_k order (:617) */
+    float* can_score_dev;   /* (B,J,5)   the refined heat ((hm+1)*hm3)*mask (:764-768) at those pixels */
+    float* can_pts_dev;     /* (B,J,5,3) self.can_pts (:771, :783): the candidates _generate_candidates (:598-627) gathers,
+                             *           point cloud + um*(0.8 - hm3*0.8), normalised */
+    float* ori_pts_dev;     /* (B,J,5,3) self.ori_pts (:781, :784): the point cloud (data/preprocess.py:189-232) at the same
+                             *           pixels, normalised */
+    float* can_weight_dev;  /* (B,J,5)   _get_candidate_weights (:629-682): raw hm at the re-projected pixel, 0 out of range */
+    float* mass_dev;        /* (B,J)     extension (no reference line): the mean-shift kernel mass sum_i exp(-|p_i - c|^2 /
+                             *           (2*0.4^2)) * w_i (the weights of :715-721) at the final centre c.  Small or <= 0: the
+                             *           candidates disagree or carry no heat */
+    float* hm_peak_dev;     /* (B,J,3)   _uvd_estimation_op (:788-814) at map resolution: (u, v, value) of the maximum of the
+                             *           raw hm[b,:,:,j], no depth mask; ties -> lowest row-major index (tf.where(...)[0],
+                             *           :808-811); NaN is never selected, nothing selected -> pixel 0.  self.hm_uvd_pts (:471) is
+                             *           (u*in_hw/map_hw, v*in_hw/map_hw, 1) */
+};
+/* dr_vote plus the report, one launch of vote_report_kernel: same contract, same xyz_mm bits.  report must not be NULL
+ * (DR_E_INVALID); maps above 4096 pixels are DR_E_UNSUPPORTED as in dr_vote. */
+int dr_vote_report(dr_handle* h, int B, const float* hm_dev, const float* hm3_dev, const float* um_dev,
+                   const float* dm_norm_dev, const float* cfg_dev, const float* com_dev, float* xyz_mm_dev,
+                   const struct dr_vote_report* report, dr_stream stream);
+/* dr_infer plus the report: forward(eval) + vote_report_kernel without materialising dense maps.  Always plain launches
+ * (never recorded into or replayed from a DR_GRAPHS=1 graph), so no launch recorded for other report buffers can run. */
+int dr_infer_report(dr_handle* h, int B, const float* dm_norm_dev, const float* cfg_dev, const float* com_dev,
+                    float* xyz_mm_dev, const struct dr_vote_report* report, dr_stream stream);
+
 /* ---- training (handle created with training=1) -------------------------------------------------- */
 enum { DR_DROPOUT_OFF = 0, DR_DROPOUT_MASK = 1, DR_DROPOUT_RNG = 2 };
 /* detect_net(..., is_training=True): batch-statistics BatchReNorm (updates moving stats, r_max,
