@@ -36,6 +36,19 @@ VOTE_REPORT_FIELDS = {'xyz_norm': ((3,), False), 'uvd': ((3,), False), 'can_idx'
                       'hm_peak': ((3,), False)}
 
 
+class DrLossReport(C.Structure):
+    """include/densereg.h: struct dr_loss_report -- device addresses, None / 0 = member not wanted."""
+    _fields_ = [(n, C.c_void_p) for n in ('total_dev', 'stack_losses_dev', 'joint_losses_dev', 'crop_losses_dev', 'gt_hm_dev',
+                                           'gt_hm3_dev', 'gt_um_dev')]
+
+
+# member of DrLossReport without its _dev suffix -> shape rule f(B, S, J, m), m = map side
+LOSS_REPORT_FIELDS = {'total': lambda B, S, J, m: (3,), 'stack_losses': lambda B, S, J, m: (S, 3),
+                      'joint_losses': lambda B, S, J, m: (S, J, 3), 'crop_losses': lambda B, S, J, m: (B, S, 3),
+                      'gt_hm': lambda B, S, J, m: (B, m, m, J), 'gt_hm3': lambda B, S, J, m: (B, m, m, J),
+                      'gt_um': lambda B, S, J, m: (B, m, m, 3 * J)}
+
+
 class KernelStat(C.Structure):
     _fields_ = [('name', C.c_char * 64), ('launches', C.c_int64), ('total_ms', C.c_double), ('flops', C.c_double),
                 ('bytes', C.c_double)]
@@ -82,6 +95,8 @@ SIGNATURES = {
     'dr_infer': (_i, [_vp, _i, _fp, _fp, _fp, _fp, _vp]),
     'dr_vote_report': (_i, [_vp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.POINTER(DrVoteReport), _vp]),
     'dr_infer_report': (_i, [_vp, _i, _fp, _fp, _fp, _fp, C.POINTER(DrVoteReport), _vp]),
+    'dr_targets': (_i, [_vp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp]),
+    'dr_loss_report': (_i, [_vp, _i, _fp, _fp, _fp, _fp, C.POINTER(DrLossReport), _vp]),
     'dr_forward_train': (_i, [_vp, _i, _fp, _i, _vp, C.c_uint64, _vp]),
     'dr_loss': (_i, [_vp, _i, _fp, _fp, _fp, _fp, _fp, _vp]),
     'dr_backward': (_i, [_vp, _i, _vp]),

@@ -20,6 +20,7 @@
 #include "kernels_misc.h"
 #include "net.h"
 #include "train_kernels.h"
+#include "loss_report.h"
 #include "vote.h"
 
 using namespace dr;
@@ -806,7 +807,7 @@ static void free_all(dr_handle* h) {
                     (void*)h->shadow, (void*)h->wp, (void*)h->wpT, (void*)h->wp3, (void*)h->wp3T, (void*)h->fold, (void*)h->bnc,
                     (void*)h->act_arena, (void*)h->grad_arena, (void*)h->scratch, (void*)h->tiny, (void*)h->tiny_ext, (void*)h->zeros,
                     (void*)h->losses, (void*)h->reg_segs, (void*)h->loss_acc, (void*)h->bn_coef, (void*)h->wg_partial, (void*)h->fold_dev, h->pack_dev, h->zero_dev,
-                    (void*)h->g_keep_arena, (void*)h->pool_arg_arena, (void*)h->group_dev, (void*)h->bn_flags})
+                    (void*)h->g_keep_arena, (void*)h->pool_arg_arena, (void*)h->group_dev, (void*)h->bn_flags, (void*)h->loss_report_ws})
         if (p) rt::dfree(p);
     for (int l = 1; l < DR_MAX_LANES; ++l) {
         if (h->scratch_l[l]) rt::dfree(h->scratch_l[l]);
@@ -1614,6 +1615,48 @@ static int infer_launches(dr_handle* h, int B, const float* dm, const float* cfg
     return vote_impl(h, B, a.fwd(), b.fwd(), c.fwd(), h->tiny, cfg, com, xyz, s, report);
 }
 
+// dr_targets / dr_loss_report (loss_report.h): one launch for the targets; when a loss member is wanted the same launch also leaves
+// fp64 partial sums per (crop, chunk, stack, joint, term), which two small launches add up in a fixed order.  Reads the maps of the
+// bound slot and writes nothing the handle owns but the report's workspace.  Accounted under the loss's kernel id.
+static int loss_report_launches(dr_handle* h, int B, const float* dm, const float* pose, const float* cfg, const float* com,
+                                const struct dr_loss_report& r, hipStream_t s) {
+    DR_ENTER(h);
+    LossReportParams lp{};
+    lp.S = h->cfg.num_stack; lp.B = B; lp.h = h->map_hw; lp.w = h->map_hw; lp.J = h->cfg.num_jnt; lp.in_hw = h->cfg.in_hw;
+    lp.dm = dm; lp.pose = pose; lp.cfg = cfg; lp.com = com;
+    lp.gt_hm = r.gt_hm_dev; lp.gt_hm3 = r.gt_hm3_dev; lp.gt_um = r.gt_um_dev;
+    const int npix = lp.h * lp.w, nchunk = dr_ceil_div(npix * lp.J, 256);
+    const double map_bytes = 4.0 * B * npix * lp.J * ((lp.gt_hm ? 1 : 0) + (lp.gt_hm3 ? 1 : 0) + (lp.gt_um ? 3 : 0));
+    if (!(r.total_dev || r.stack_losses_dev || r.joint_losses_dev || r.crop_losses_dev)) {
+        ProfScope ps(h, s, KID_LOSS, 0.0, map_bytes + 4.0 * B * npix);
+        DR_LAUNCH(targets_kernel, dim3(nchunk, B), dim3(256), 0, s, lp);
+        DR_CHECK_LAUNCH(h);
+        return DR_OK;
+    }
+    const size_t n = (size_t)lp.S * lp.J * 3, MB = (size_t)h->cfg.max_batch;
+    if (!h->loss_report_ws) {
+        h->loss_report_ws = (double*)rt::dmalloc((MB * nchunk * n + MB * n + MB * lp.S * 3) * sizeof(double));
+        if (!h->loss_report_ws) DR_FAIL(h, DR_E_NOMEM, "dr_loss_report: no device memory for the partial sums");
+    }
+    double* part = h->loss_report_ws;
+    double* bsj = part + MB * nchunk * n;
+    double* cropd = bsj + MB * n;
+    for (int i = 0; i < lp.S; ++i) {
+        TView a{h->hm[i], 0, h->hm[i]->C}, b{h->hm3[i], 0, h->hm3[i]->C}, c{h->um[i], 0, h->um[i]->C};
+        lp.hm[i] = a.fwd(); lp.hm3[i] = b.fwd(); lp.um[i] = c.fwd();
+    }
+    lp.part = part;
+    if (h->pipe_depth == 2 && h->slot[h->cur_slot].fwd_recorded) rt::stream_wait_event(s, h->slot[h->cur_slot].fwd_done);
+    ProfScope ps(h, s, KID_LOSS, 0.0, 4.0 * B * npix * lp.S * 5.0 * lp.J + map_bytes + 4.0 * B * npix);
+    DR_LAUNCH(loss_report_kernel, dim3(nchunk, B), dim3(256), 0, s, lp);
+    DR_LAUNCH(loss_report_crop_kernel, dim3(B), dim3(256), 0, s, (const double*)part, nchunk, lp.S, lp.J, bsj, cropd, r.crop_losses_dev);
+    if (r.total_dev || r.stack_losses_dev || r.joint_losses_dev)
+        DR_LAUNCH(loss_report_out_kernel, dim3(1), dim3(256), 0, s, (const double*)bsj, (const double*)cropd, B, lp.S, lp.J,
+                  r.joint_losses_dev, r.stack_losses_dev, r.total_dev);
+    DR_CHECK_LAUNCH(h);
+    return DR_OK;
+}
+
 extern "C" {
 
 int dr_forward_eval(dr_handle* h, int B, const float* dm, float* hm, float* hm3, float* um, dr_stream stream) {
@@ -1665,6 +1708,31 @@ int dr_infer_report(dr_handle* h, int B, const float* dm, const float* cfg, cons
     if (!h || !dm || !cfg || !com || !xyz) return DR_E_INVALID;
     if (!report) DR_FAIL(h, DR_E_INVALID, "dr_infer_report: report is NULL (dr_infer is the entry point without one)");
     return infer_launches(h, B, dm, cfg, com, xyz, report, (hipStream_t)stream);
+}
+
+int dr_targets(dr_handle* h, int B, const float* dm, const float* pose, const float* cfg, const float* com, float* gt_hm,
+               float* gt_hm3, float* gt_um, dr_stream stream) {
+    if (!h || !dm || !pose || !cfg || !com) return DR_E_INVALID;
+    if (!gt_hm && !gt_hm3 && !gt_um) DR_FAIL(h, DR_E_INVALID, "dr_targets: no output wanted");
+    if (B < 1 || B > h->cfg.max_batch) DR_FAIL(h, DR_E_INVALID, "batch %d outside [1, max_batch=%d]", B, h->cfg.max_batch);
+    struct dr_loss_report r{};
+    r.gt_hm_dev = gt_hm; r.gt_hm3_dev = gt_hm3; r.gt_um_dev = gt_um;
+    return loss_report_launches(h, B, dm, pose, cfg, com, r, (hipStream_t)stream);
+}
+
+// Launches directly, like dr_infer_report: the report's pointers are baked into the launches.
+int dr_loss_report(dr_handle* h, int B, const float* dm, const float* pose, const float* cfg, const float* com,
+                   const struct dr_loss_report* report, dr_stream stream) {
+    if (!h || !dm || !pose || !cfg || !com) return DR_E_INVALID;
+    if (!report) DR_FAIL(h, DR_E_INVALID, "dr_loss_report: report is NULL");
+    const struct dr_loss_report& r = *report;
+    if (!r.total_dev && !r.stack_losses_dev && !r.joint_losses_dev && !r.crop_losses_dev && !r.gt_hm_dev && !r.gt_hm3_dev && !r.gt_um_dev)
+        DR_FAIL(h, DR_E_INVALID, "dr_loss_report: every member of the report is NULL");
+    if (B < 1 || B > h->cfg.max_batch) DR_FAIL(h, DR_E_INVALID, "batch %d outside [1, max_batch=%d]", B, h->cfg.max_batch);
+    if (h->cfg.num_stack > kMaxStack) DR_FAIL(h, DR_E_UNSUPPORTED, "more than %d stacks", kMaxStack);
+    if (h->last_B < 1) DR_FAIL(h, DR_E_STATE, "dr_loss_report needs a forward first");
+    if (B != h->last_B) DR_FAIL(h, DR_E_STATE, "dr_loss_report: B=%d but the last forward ran %d", B, h->last_B);
+    return loss_report_launches(h, B, dm, pose, cfg, com, r, (hipStream_t)stream);
 }
 
 int dr_read_activation(dr_handle* h, const char* scope, int B, float* host, size_t count) {

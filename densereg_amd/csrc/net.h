@@ -205,6 +205,8 @@ struct dr_handle {
     float* tiny_ext = nullptr;                              // same, for dr_vote on external maps
     float* zeros = nullptr;                                 // 256 B of zeros: target of predicated-off loads
     float* losses = nullptr;                                // 4 floats (device)
+    double* loss_report_ws = nullptr;                       // dr_loss_report: partial sums per (crop, chunk, stack, joint, term) | per (crop, stack,
+                                                            // joint, term) | per (crop, stack, term); allocated by the first call, for max_batch
     const float* dm_in = nullptr;                           // input of the last forward (not owned)
 
     // network outputs per stack (dense-ish tensors)

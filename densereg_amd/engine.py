@@ -54,6 +54,19 @@ class VoteReport(NamedTuple):
         return torch.cat([uv, torch.ones_like(uv[..., :1])], dim=-1).reshape(uv.shape[0], -1)
 
 
+class LossReport(NamedTuple):
+    """What ``Engine.loss_report`` fetches (``struct dr_loss_report``): the l2 losses of the most recent forward (hourglass_um_crop_tiny.py
+    :353, :357, :363; last axis = hm, hm3, um) and the targets they were taken against (:336-346).  Members that were not asked
+    for are ``None``."""
+    total: Optional[torch.Tensor]           # (3)         summed over stacks: the first three terms of ``Engine.loss``
+    stack_losses: Optional[torch.Tensor]    # (S,3)
+    joint_losses: Optional[torch.Tensor]    # (S,J,3)
+    crop_losses: Optional[torch.Tensor]     # (B,S,3)
+    gt_hm: Optional[torch.Tensor]           # (B,h,w,J)   self.gt_hms
+    gt_hm3: Optional[torch.Tensor]          # (B,h,w,J)   self.gt_hm3s
+    gt_um: Optional[torch.Tensor]           # (B,h,w,3J)  self.gt_ums
+
+
 class Engine:
     """One engine per (process, device).  Mirrors the call sites of the reference:
 
@@ -207,6 +220,37 @@ class Engine:
         rep, c_rep = self._new_report(B, fields)
         self.h.call('dr_infer_report', B, _p(dm_norm), _p(cfg), _p(com), _p(xyz), C.byref(c_rep), self._stream())
         return xyz, rep
+
+    def _new_loss_report(self, B: int, fields: Optional[Iterable[str]], known):
+        """As ``_new_report``, for ``struct dr_loss_report``; ``known`` = the members this entry point offers."""
+        want = tuple(known) if fields is None else tuple(fields)
+        unknown = [f for f in want if f not in known]
+        if unknown:
+            raise ValueError('unknown loss report member(s) %s; known: %s' % (unknown, ', '.join(known)))
+        bufs, c_rep = {}, _lib.DrLossReport()
+        for name, shape in _lib.LOSS_REPORT_FIELDS.items():
+            bufs[name] = self.new(*shape(B, self.num_stack, self.num_jnt, self.map_hw)) if name in want else None
+            setattr(c_rep, name + '_dev', _p(bufs[name]))
+        return LossReport(**bufs), c_rep
+
+    def targets(self, dm_norm, pose_mm, cfg, com, fields: Optional[Iterable[str]] = None):
+        """The training targets as maps (``dr_targets``): ``(gt_hm, gt_hm3, gt_um)``; needs no forward and no parameters.
+        ``fields`` names the maps to build (default: all three); the others are ``None``."""
+        B = dm_norm.shape[0]
+        rep, c = self._new_loss_report(B, fields, ('gt_hm', 'gt_hm3', 'gt_um'))
+        self.h.call('dr_targets', B, _p(_f32(dm_norm)), _p(_f32(pose_mm)), _p(_f32(cfg)), _p(_f32(com)), c.gt_hm_dev, c.gt_hm3_dev,
+                    c.gt_um_dev, self._stream())
+        return rep.gt_hm, rep.gt_hm3, rep.gt_um
+
+    def loss_report(self, dm_norm, pose_mm, cfg, com, fields: Optional[Iterable[str]] = None) -> LossReport:
+        """The loss terms of the most recent forward -- eval or train -- per stack, joint and crop, and the targets
+        (``dr_loss_report``).  Changes nothing in the engine: a validation loss after ``forward_eval`` / ``infer``, or a closer look
+        at a training micro-step between ``forward_train`` and ``backward``.  ``fields`` as in ``vote_report``."""
+        B = dm_norm.shape[0]
+        rep, c_rep = self._new_loss_report(B, fields, tuple(_lib.LOSS_REPORT_FIELDS))
+        self.h.call('dr_loss_report', B, _p(_f32(dm_norm)), _p(_f32(pose_mm)), _p(_f32(cfg)), _p(_f32(com)), C.byref(c_rep),
+                    self._stream())
+        return rep
 
     def read_activation(self, scope: str, B: int, shape) -> np.ndarray:
         torch.cuda.synchronize(self.device)

@@ -138,15 +138,23 @@ class JointDetectionModel(object):
         and ``unnorm_xyz_pose`` (:462) are inside the kernel.  Returns xyz in mm, (B, 3J)."""
         return self.engine.vote(hms, hm3s, ums, dms, cfgs, coms)
 
-    def test(self, dms, poses, cfgs, coms, report=False):
+    def test(self, dms, poses, cfgs, coms, report=False, losses=False):
         """(:442-462) depth (mm) -> xyz (mm).  ``report=True`` also sets the reference's fetch interface (:521-526, :783-784):
         ``self.uvd_pts`` (B,J,3), ``self.can_pts`` / ``self.ori_pts`` (B,J,5,3) and ``self.hm_uvd_pts`` (B,3J), written by the
-        vote's own launch."""
+        vote's own launch.  ``losses=True`` also sets, from one loss report on the maps the inference left behind, the validation
+        losses ``self.val_losses`` (3) / ``self.val_stack_losses`` (S,3) / ``self.val_joint_losses`` (S,J,3) (:353-363 in eval mode;
+        last axis hm, hm3, um) and the targets ``self.gt_hms`` / ``self.gt_hm3s`` / ``self.gt_ums`` (:475-480)."""
         normed = self.engine.norm_dm(dms, coms)
         if not report:
-            return self.engine.infer(normed, cfgs, coms)
-        xyz, rep = self.engine.infer_report(normed, cfgs, coms, fields=('uvd', 'can_pts', 'ori_pts', 'hm_peak'))
-        self.uvd_pts, self.can_pts, self.ori_pts, self.hm_uvd_pts = rep.uvd, rep.can_pts, rep.ori_pts, rep.hm_uvd_pts
+            xyz = self.engine.infer(normed, cfgs, coms)
+        else:
+            xyz, rep = self.engine.infer_report(normed, cfgs, coms, fields=('uvd', 'can_pts', 'ori_pts', 'hm_peak'))
+            self.uvd_pts, self.can_pts, self.ori_pts, self.hm_uvd_pts = rep.uvd, rep.can_pts, rep.ori_pts, rep.hm_uvd_pts
+        if losses:
+            lr = self.engine.loss_report(normed, poses, cfgs, coms,
+                                         fields=('total', 'stack_losses', 'joint_losses', 'gt_hm', 'gt_hm3', 'gt_um'))
+            self.val_losses, self.val_stack_losses, self.val_joint_losses = lr.total, lr.stack_losses, lr.joint_losses
+            self.gt_hms, self.gt_hm3s, self.gt_ums = lr.gt_hm, lr.gt_hm3, lr.gt_um
         return xyz
 
     def loss(self, dms, poses, cfgs, coms, seed=0):

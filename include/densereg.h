@@ -218,6 +218,37 @@ int dr_flat_adam(dr_handle* h, float** m_dev_ptr, float** v_dev_ptr, size_t* cou
  * weights for the next forward. */
 int dr_apply_adam(dr_handle* h, float lr, float div, float clip, int64_t step, dr_stream stream);
 
+/* ---- loss report (any handle) --------------------------------------------------------------------- */
+/* _hm_2d / _hm_3d / _um (hourglass_um_crop_tiny.py:195-274) on the point cloud of dm_norm: the targets JointDetectionModel.loss
+ * (:336-346) and .test (:474-480) build.  Any handle (training = 0 too), no forward needed, no parameters needed.  dm_norm
+ * (B,hw,hw,1), pose_mm (B,3J), cfg (B,6), com (B,3).  Outputs nullable, at least one wanted (else DR_E_INVALID): gt_hm (B,h,w,J),
+ * gt_hm3 (B,h,w,J), gt_um (B,h,w,3J), h = w = in_hw/4.  One launch on `stream`. */
+int dr_targets(dr_handle* h, int B, const float* dm_norm_dev, const float* pose_mm_dev, const float* cfg_dev,
+               const float* com_dev, float* gt_hm_dev, float* gt_hm3_dev, float* gt_um_dev, dr_stream stream);
+
+/* Device pointers, any member NULL = not wanted; dense, row-major float32; S = num_stack, J = num_jnt; the three terms of the
+ * last axis are hm, hm3, um (l2_loss = sum(x^2)/2, :353, :357, :363).  The struct is read during the call.  (A struct tag, not a
+ * typedef, as dr_vote_report.) */
+struct dr_loss_report {
+    float* total_dev;           /* (3)      summed over stacks: dr_loss's first three terms */
+    float* stack_losses_dev;    /* (S,3)    the per-stack terms before they are summed */
+    float* joint_losses_dev;    /* (S,J,3)  the same split by joint (um: its three channels together) */
+    float* crop_losses_dev;     /* (B,S,3)  the same split by crop */
+    float* gt_hm_dev;           /* (B,h,w,J)   the targets of dr_targets, written by the same launch */
+    float* gt_hm3_dev;          /* (B,h,w,J)  */
+    float* gt_um_dev;           /* (B,h,w,3J) */
+};
+/* The loss terms of the MOST RECENT forward of this handle -- eval or train, training or inference handle -- against the targets
+ * of (dm_norm, pose, cfg, com).  Read-only with respect to the handle: writes no gradient seed, no accumulator, no BatchReNorm
+ * state, and does not advance a micro-step.  No regulariser term (dr_loss has it).  Every sum is taken in fp64 in a fixed order:
+ * two calls on the same forward give the same bits.  With micro-batch groups the sums run over all B crops (crop_losses gives
+ * the per-micro-batch view).  Stream ordering as dr_read_maps: the work runs on `stream`, at pipeline depth 2 behind the forward
+ * of the micro-step in progress; successive calls share a workspace and must be ordered by their streams.  Always plain
+ * launches (never part of a DR_GRAPHS=1 graph).  DR_E_INVALID: report NULL or without any member, B outside [1, max_batch];
+ * DR_E_STATE: no forward yet, or B differs from the last forward's; DR_E_UNSUPPORTED: more than 8 stacks, as dr_loss. */
+int dr_loss_report(dr_handle* h, int B, const float* dm_norm_dev, const float* pose_mm_dev, const float* cfg_dev,
+                   const float* com_dev, const struct dr_loss_report* report, dr_stream stream);
+
 /* ---- dataset formats: PNG depth frames out of the TFRecord files --------------------------- */
 /* Host: undo the PNG row filters (PNG spec 9.2) of an inflated IDAT stream.  `filtered` = height rows of
  * (1 filter-type byte + row_bytes), bpp = bytes per pixel (3 for NYU's RGB8, 2 for 16-bit grey); out = height*row_bytes
