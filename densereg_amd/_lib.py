@@ -49,6 +49,22 @@ LOSS_REPORT_FIELDS = {'total': lambda B, S, J, m: (3,), 'stack_losses': lambda B
                       'gt_um': lambda B, S, J, m: (B, m, m, 3 * J)}
 
 
+class DrStepReport(C.Structure):
+    """include/densereg.h: struct dr_step_report -- the edges in, device addresses out, None / 0 = member not wanted."""
+    _fields_ = [('hist_edges_dev', C.c_void_p), ('num_edges', C.c_int32)] + [(n, C.c_void_p) for n in (
+        'param_stats_dev', 'grad_stats_dev', 'raw_stats_dev', 'update_stats_dev', 'grad_counts_dev', 'global_dev',
+        'global_counts_dev', 'grad_hist_dev', 'param_hist_dev')]
+
+
+# output member of DrStepReport without its _dev suffix -> (shape rule f(V, E), is_int32); V = trainable variables, E = edges
+STEP_REPORT_FIELDS = {'param_stats': (lambda V, E: (V, 4), False), 'grad_stats': (lambda V, E: (V, 4), False),
+                      'raw_stats': (lambda V, E: (V, 2), False), 'update_stats': (lambda V, E: (V, 4), False),
+                      'grad_counts': (lambda V, E: (V, 4), True), 'global': (lambda V, E: (6,), False),
+                      'global_counts': (lambda V, E: (3,), True), 'grad_hist': (lambda V, E: (V, E + 1), True),
+                      'param_hist': (lambda V, E: (V, E + 1), True)}
+STEP_REPORT_MAX_EDGES = 2048
+
+
 class KernelStat(C.Structure):
     _fields_ = [('name', C.c_char * 64), ('launches', C.c_int64), ('total_ms', C.c_double), ('flops', C.c_double),
                 ('bytes', C.c_double)]
@@ -107,6 +123,7 @@ SIGNATURES = {
     'dr_flat_grad': (_i, [_vp, C.POINTER(_vp), C.POINTER(_sz)]),
     'dr_flat_param': (_i, [_vp, C.POINTER(_vp), C.POINTER(_sz)]),
     'dr_apply_adam': (_i, [_vp, C.c_float, C.c_float, C.c_float, C.c_int64, _vp]),
+    'dr_step_report': (_i, [_vp, C.c_float, C.c_float, C.c_float, C.c_int64, C.POINTER(DrStepReport), _vp]),
     'dr_read_activation': (_i, [_vp, C.c_char_p, _i, _fp, _sz]),
     'dr_conv_flops_per_crop': (C.c_double, [_vp]),
     'dr_set_precision': (_i, [_vp, _i]),

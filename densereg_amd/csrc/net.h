@@ -119,6 +119,7 @@ enum KernelId {
     KID_CONV_X3,                     // conv_x3.h (named conv_x3_128x128: bench.py prices it against the bf16 matrix cores / 6)
     KID_WGRAD_X3_128, KID_WGRAD_X3_64,   // conv_wgrad_x3.h
     KID_CONV_P3,                     // conv_p3.h (the x3 products on a P3-stored input; priced like conv_x3_128x128)
+    KID_STEP_REPORT,                 // step_report.h (dr_step_report: all of its launches)
     KID_COUNT
 };
 static const char* const kKernelNames[KID_COUNT] = {
@@ -126,7 +127,7 @@ static const char* const kKernelNames[KID_COUNT] = {
     "conv_igemm_64x96", "conv_igemm_64x160", "conv_igemm16_64x80", "conv_igemm16_64x144", "conv_igemm16_64x160",
     "stem_conv", "maxpool",
     "upsample_add", "uvd", "copy_channels", "hourglass_tail_fused", "vote", "batch_renorm", "stem_wgrad", "wgrad_fold", "eltwise_bwd", "loss", "adam",
-    "conv_wgrad_128", "conv_wgrad_64", "conv_wgrad_row96", "conv_wgrad_group", "conv_wgrad16", "conv_x3_128x128", "conv_wgrad_x3_128", "conv_wgrad_x3_64", "conv_p3_128x128"};
+    "conv_wgrad_128", "conv_wgrad_64", "conv_wgrad_row96", "conv_wgrad_group", "conv_wgrad16", "conv_x3_128x128", "conv_wgrad_x3_128", "conv_wgrad_x3_64", "conv_p3_128x128", "step_report"};
 
 // The part of one hourglass below 16x16 pixels (hg_fused.h): in eval mode the ops [first_op, last_op] and the pool at pool_op are
 // ONE launch.  conv[]: the ConvLayer indices of its eight residual modules in execution order.
@@ -207,6 +208,9 @@ struct dr_handle {
     float* losses = nullptr;                                // 4 floats (device)
     double* loss_report_ws = nullptr;                       // dr_loss_report: partial sums per (crop, chunk, stack, joint, term) | per (crop, stack,
                                                             // joint, term) | per (crop, stack, term); allocated by the first call, for max_batch
+    void* step_report_ws = nullptr;                         // dr_step_report: chunk table | variable table | per-chunk partials
+                                                            // (step_report.h); built by the first call, the layout never changes
+    int step_nchunk = 0, step_nvar = 0;
     const float* dm_in = nullptr;                           // input of the last forward (not owned)
 
     // network outputs per stack (dense-ish tensors)

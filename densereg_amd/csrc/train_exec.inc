@@ -1038,6 +1038,13 @@ int backward_impl(dr_handle* h, int B, hipStream_t main_s) {
     return DR_OK;
 }
 
+// Adam's bias-corrected step size (beta1 = 0.5, beta2 = 0.999) as dr_apply_adam hands it to adam_kernel; dr_step_report describes
+// that step and must use the same bits
+float adam_lr_t(float lr, int64_t step) {
+    const double b1 = 0.5, b2 = 0.999;
+    return (float)((double)lr * std::sqrt(1.0 - std::pow(b2, (double)step)) / (1.0 - std::pow(b1, (double)step)));
+}
+
 }  // namespace
 
 extern "C" {
@@ -1304,8 +1311,7 @@ int dr_apply_adam(dr_handle* h, float lr, float div, float clip, int64_t step, d
         const int rc = dr_sync_grads(h, stream);
         if (rc) return rc;
     }
-    const double b1 = 0.5, b2 = 0.999;
-    const float lr_t = (float)((double)lr * std::sqrt(1.0 - std::pow(b2, (double)step)) / (1.0 - std::pow(b1, (double)step)));
+    const float lr_t = adam_lr_t(lr, step);
     {
         ProfScope ps(h, s, KID_ADAM, 0.0, 28.0 * h->n_train);
         DR_LAUNCH(adam_kernel, dim3(grid_for((long)h->n_train)), dim3(256), 0, s, h->flat_param, (const float*)h->flat_grad, h->adam_m,
@@ -1313,6 +1319,90 @@ int dr_apply_adam(dr_handle* h, float lr, float div, float clip, int64_t step, d
     }
     DR_CHECK_LAUNCH(h);
     return repack_weights(h, s);
+}
+
+// The step dr_apply_adam(h, lr, div, clip, step, stream) would take now, described and not taken (step_report.h).  Reads both
+// slots' accumulators where dr_apply_adam would first merge them; writes nothing the handle owns but the report's workspace.
+int dr_step_report(dr_handle* h, float lr, float div, float clip, int64_t step, const struct dr_step_report* report, dr_stream stream) {
+    if (!h) return DR_E_INVALID;
+    if (!h->cfg.training) DR_FAIL(h, DR_E_STATE, "dr_step_report: handle was created with training=0");
+    if (!report) DR_FAIL(h, DR_E_INVALID, "dr_step_report: report is NULL");
+    const struct dr_step_report& r = *report;
+    const bool want_global = r.global_dev || r.global_counts_dev;
+    if (!r.param_stats_dev && !r.grad_stats_dev && !r.raw_stats_dev && !r.update_stats_dev && !r.grad_counts_dev && !want_global &&
+        !r.grad_hist_dev && !r.param_hist_dev)
+        DR_FAIL(h, DR_E_INVALID, "dr_step_report: every output member of the report is NULL");
+    if (step < 1 || !(div > 0.f) || !(clip > 0.f)) DR_FAIL(h, DR_E_INVALID, "dr_step_report: step must be >= 1, div > 0 and clip > 0");
+    if (r.num_edges < 0 || r.num_edges > kStepMaxEdges) DR_FAIL(h, DR_E_INVALID, "dr_step_report: num_edges %d outside [0, %d]", r.num_edges, kStepMaxEdges);
+    if ((r.grad_hist_dev || r.param_hist_dev) && r.num_edges == 0) DR_FAIL(h, DR_E_INVALID, "dr_step_report: a histogram needs num_edges > 0");
+    if (r.num_edges > 0 && !r.hist_edges_dev) DR_FAIL(h, DR_E_INVALID, "dr_step_report: num_edges > 0 but hist_edges_dev is NULL");
+    DR_ENTER(h);
+    hipStream_t s = (hipStream_t)stream;
+    if (!h->step_report_ws) {                                  // the chunk table: once per handle (the flat layout never changes)
+        std::vector<StepChunk> chunks;
+        std::vector<StepVar> vars;
+        long off = 0;
+        for (auto& p : h->params) {
+            if (!p.trainable) continue;
+            StepVar v{(long)p.count, (int)chunks.size(), 0};
+            for (long b = 0; b < (long)p.count; b += kStepChunk)
+                chunks.push_back(StepChunk{off + b, off + std::min<long>(b + kStepChunk, (long)p.count), (int)vars.size(), 0});
+            v.nchunk = (int)chunks.size() - v.first_chunk;
+            vars.push_back(v);
+            off += (long)p.count;
+        }
+        if (off != (long)h->n_train) DR_FAIL(h, DR_E_STATE, "dr_step_report: the variables do not add up to the flat buffer");
+        const size_t nb_ck = chunks.size() * sizeof(StepChunk), nb_var = vars.size() * sizeof(StepVar);
+        char* ws = (char*)rt::dmalloc(nb_ck + nb_var + chunks.size() * sizeof(StepPart));
+        if (!ws) DR_FAIL(h, DR_E_NOMEM, "dr_step_report: no device memory for the workspace");
+        if (rt::h2d(ws, chunks.data(), nb_ck, s) || rt::h2d(ws + nb_ck, vars.data(), nb_var, s)) {
+            rt::sync_stream(s);
+            rt::dfree(ws);
+            DR_FAIL(h, DR_E_DEVICE, "dr_step_report: h2d of the chunk table failed");
+        }
+        rt::sync_stream(s);                                    // the tables are host memory that goes away; only on the first call
+        h->step_report_ws = ws; h->step_nchunk = (int)chunks.size(); h->step_nvar = (int)vars.size();
+    }
+    static_assert(sizeof(StepChunk) % 8 == 0 && sizeof(StepVar) % 8 == 0 && sizeof(StepPart) % 8 == 0, "the workspace parts stay 8-byte aligned");
+    const int nck = h->step_nchunk, V = h->step_nvar, E = r.num_edges;
+    char* ws = (char*)h->step_report_ws;
+    const StepChunk* chunks = (const StepChunk*)ws;
+    const StepVar* vars = (const StepVar*)(ws + nck * sizeof(StepChunk));
+    StepPart* part = (StepPart*)(ws + nck * sizeof(StepChunk) + V * sizeof(StepVar));
+
+    pipeline_join(h, s);                                       // as dr_sync_grads: behind every micro-step in flight
+    StepReportParams sp{};
+    sp.grad = h->flat_grad;
+    sp.grad2 = (h->pipe_depth == 2 && h->slot[1].grads_dirty) ? h->slot[1].gacc : nullptr;   // read, neither folded nor cleared
+    sp.param = h->flat_param; sp.m = h->adam_m; sp.v = h->adam_v;
+    sp.chunks = chunks; sp.part = part;
+    sp.edges = r.hist_edges_dev; sp.E = E; sp.grad_hist = r.grad_hist_dev; sp.param_hist = r.param_hist_dev;
+    sp.div = div; sp.clip = clip; sp.lr_t = adam_lr_t(lr, step); sp.b1 = 0.5f; sp.b2 = 0.999f; sp.eps = 1e-8f;
+    // which of theta / acc / (m, v) are read at all: members that are NULL cost no loads
+    const int need_param = (r.param_stats_dev || r.param_hist_dev || r.global_dev) ? 1 : 0;
+    const int need_upd = (r.update_stats_dev || r.global_dev) ? 1 : 0;
+    const int need_grad = (r.grad_stats_dev || r.raw_stats_dev || r.grad_counts_dev || r.grad_hist_dev || want_global || need_upd) ? 1 : 0;
+    const int mode = need_param * kStepParam + need_grad * kStepGrad + need_upd * kStepUpd + ((r.grad_hist_dev || r.param_hist_dev) ? kStepHist : 0);
+    const size_t hist_bytes = (size_t)V * (E + 1) * sizeof(int32_t);
+    const size_t smem = (r.grad_hist_dev || r.param_hist_dev)
+                            ? (size_t)E * sizeof(float) + (size_t)(E + 1) * sizeof(int) * ((r.grad_hist_dev ? 1 : 0) + (r.param_hist_dev ? 1 : 0)) : 0;
+    ProfScope ps(h, s, KID_STEP_REPORT, 0.0,
+                 4.0 * h->n_train * (need_param + need_grad * (sp.grad2 ? 2 : 1) + 2 * need_upd));
+    if (r.grad_hist_dev) rt::memset_async(r.grad_hist_dev, 0, hist_bytes, s);      // the chunks ADD their bucket counts
+    if (r.param_hist_dev) rt::memset_async(r.param_hist_dev, 0, hist_bytes, s);
+    switch (mode) {                                            // (an update needs the gradient: six of these never occur)
+#define DR_STEP_MODE(M) case M: DR_LAUNCH(step_report_kernel<M>, dim3(nck), dim3(256), smem, s, sp); break;
+        DR_STEP_MODE(1) DR_STEP_MODE(2) DR_STEP_MODE(3) DR_STEP_MODE(6) DR_STEP_MODE(7)
+        DR_STEP_MODE(9) DR_STEP_MODE(10) DR_STEP_MODE(11) DR_STEP_MODE(14) DR_STEP_MODE(15)
+#undef DR_STEP_MODE
+        default: DR_FAIL(h, DR_E_STATE, "dr_step_report: no kernel for member mode %d", mode);
+    }
+    StepFoldOut fo{r.param_stats_dev, r.grad_stats_dev, r.raw_stats_dev, r.update_stats_dev, r.grad_counts_dev, r.global_dev, r.global_counts_dev};
+    const int n_var_blocks = (fo.param_stats || fo.grad_stats || fo.raw_stats || fo.update_stats || fo.grad_counts) ? V : 0;
+    if (n_var_blocks + (want_global ? 1 : 0) > 0)
+        DR_LAUNCH(step_report_fold_kernel, dim3(n_var_blocks + (want_global ? 1 : 0)), dim3(256), 0, s, (const StepPart*)part, vars, n_var_blocks, nck, fo);
+    DR_CHECK_LAUNCH(h);
+    return DR_OK;
 }
 
 }  // extern "C"

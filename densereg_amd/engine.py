@@ -67,6 +67,46 @@ class LossReport(NamedTuple):
     gt_um: Optional[torch.Tensor]           # (B,h,w,3J)  self.gt_ums
 
 
+class StepReport(NamedTuple):
+    """What ``Engine.step_report`` fetches (``struct dr_step_report``): per trainable variable (``names``, flat order) the statistics
+    of the weights, of the averaged and clipped gradient ``g`` and of the decrement ``u`` the next ``apply_adam`` would apply --
+    the reference's per-variable histograms (train_single_gpu.py:91-95) and the counts that show a diverging or dead layer before
+    the step is taken.  Members that were not asked for are ``None``."""
+    param_stats: Optional[torch.Tensor]     # (V,4)   min, max, sum, sum of squares of theta
+    grad_stats: Optional[torch.Tensor]      # (V,4)   the same of g
+    raw_stats: Optional[torch.Tensor]       # (V,2)   max |a|, sum a^2 over the finite a = acc / div (before the clip)
+    update_stats: Optional[torch.Tensor]    # (V,4)   min, max, sum, sum of squares of u
+    grad_counts: Optional[torch.Tensor]     # (V,4)   int32: elements, non-finite acc, clipped, acc == 0
+    global_: Optional[torch.Tensor]         # (6)     ||g||, ||a|| (finite a), ||theta||, ||u||, max |g|, max |u|   (member ``global``)
+    global_counts: Optional[torch.Tensor]   # (3)     int32: non-finite, clipped, zero
+    grad_hist: Optional[torch.Tensor]       # (V,E+1) int32 bucket counts of g: bucket = np.searchsorted(edges, x, side='right')
+    param_hist: Optional[torch.Tensor]      # (V,E+1) int32 bucket counts of theta
+    names: tuple                            # the V variable names
+    edges: Optional[torch.Tensor]           # (E) the histogram edges on the device (may be passed back as ``edges``), or None
+
+    def get(self, member: str):
+        """Member by its name in ``_lib.STEP_REPORT_FIELDS`` (``global`` is a Python keyword: the attribute is ``global_``)."""
+        return getattr(self, 'global_' if member == 'global' else member)
+
+
+def hist_edges(lo: float = 1e-12, hi: float = 1e20, ratio: float = 1.1) -> np.ndarray:
+    """The symmetric geometric edge set ``-hi ... -lo, +lo ... +hi`` (float32, strictly ascending): ``2 * ceil(log(hi / lo) /
+    log(ratio))`` edges, geometrically spaced from ``lo`` to ``hi`` on either side (buckets about ``ratio`` wide) and one bucket
+    ``[-lo, +lo)`` around zero.  Buckets follow numpy (``Engine.step_report``)."""
+    if not (0.0 < lo < hi and ratio > 1.0):
+        raise ValueError('hist_edges: need 0 < lo < hi and ratio > 1')
+    n = int(np.ceil(np.log(hi / lo) / np.log(ratio)))
+    pos = np.geomspace(lo, hi, n).astype(np.float32)
+    e = np.concatenate([-pos[::-1], pos])
+    if e.size > _lib.STEP_REPORT_MAX_EDGES or not np.all(np.isfinite(e)) or not np.all(np.diff(e) > 0):
+        raise ValueError('hist_edges(%g, %g, %g): %d edges; at most %d strictly ascending finite float32 values can be used'
+                         % (lo, hi, ratio, e.size, _lib.STEP_REPORT_MAX_EDGES))
+    return e
+
+
+assert hist_edges().size <= _lib.STEP_REPORT_MAX_EDGES
+
+
 class Engine:
     """One engine per (process, device).  Mirrors the call sites of the reference:
 
@@ -302,6 +342,57 @@ class Engine:
 
     def apply_adam(self, lr: float, div: float, step: int, clip: float = 0.2):
         self.h.call('dr_apply_adam', C.c_float(lr), C.c_float(div), C.c_float(clip), C.c_int64(step), self._stream())
+
+    def trainable_names(self) -> tuple:
+        """The trainable variables in flat order (the rows of every per-variable member of ``step_report``)."""
+        if getattr(self, '_trainable_names', None) is None:
+            self._trainable_names = tuple(n for n, _, tr in self.h.param_infos() if tr)
+        return self._trainable_names
+
+    def _device_edges(self, edges) -> Optional[torch.Tensor]:
+        """Histogram edges checked on the host (strictly ascending, finite, at most 2048) and uploaded.  The tensor a previous
+        report returned as ``StepReport.edges`` is taken as it is: it was checked then."""
+        if edges is None:
+            return None
+        if edges is getattr(self, '_step_edges', None):
+            return edges
+        e = edges.detach().cpu().numpy() if isinstance(edges, torch.Tensor) else np.asarray(edges)
+        e = np.ascontiguousarray(e, np.float32).reshape(-1)
+        if e.size < 1 or e.size > _lib.STEP_REPORT_MAX_EDGES:
+            raise ValueError('step report: %d histogram edges (1..%d)' % (e.size, _lib.STEP_REPORT_MAX_EDGES))
+        if not np.all(np.isfinite(e)) or not np.all(e[1:] > e[:-1]):
+            raise ValueError('step report: the histogram edges must be finite and strictly ascending')
+        self._step_edges = torch.from_numpy(e).to(self.device)
+        return self._step_edges
+
+    def step_report(self, lr: float, div: float, step: int, clip: float = 0.2, fields: Optional[Iterable[str]] = None,
+                    edges=None) -> StepReport:
+        """The step ``apply_adam(lr, div, step, clip)`` would take now, described and not taken (``dr_step_report``): changes
+        nothing in the engine.  ``fields`` names the members to fetch (``_lib.STEP_REPORT_FIELDS``; default: all, the two
+        histograms only when ``edges`` are given); the others are ``None`` and cost nothing.  ``edges``: strictly ascending finite
+        histogram edges (``hist_edges()``), a host array or the device tensor of an earlier report; element ``x`` is counted in
+        bucket ``np.searchsorted(edges, x, side='right')``."""
+        known = _lib.STEP_REPORT_FIELDS
+        if fields is None:
+            want = tuple(n for n in known if edges is not None or not n.endswith('_hist'))
+        else:
+            want = tuple(fields)
+        unknown = [f for f in want if f not in known]
+        if unknown:
+            raise ValueError('unknown step report member(s) %s; known: %s' % (unknown, ', '.join(known)))
+        if edges is None and any(n.endswith('_hist') for n in want):
+            raise ValueError('step report: a histogram member needs edges')
+        d_edges = self._device_edges(edges)
+        names = self.trainable_names()
+        V, E = len(names), 0 if d_edges is None else int(d_edges.numel())
+        bufs, c_rep = {}, _lib.DrStepReport()
+        c_rep.hist_edges_dev, c_rep.num_edges = _p(d_edges), E
+        for name, (shape, is_int) in known.items():
+            t = self.new(*shape(V, E), dtype=torch.int32 if is_int else torch.float32) if name in want else None
+            bufs['global_' if name == 'global' else name] = t
+            setattr(c_rep, name + '_dev', _p(t))
+        self.h.call('dr_step_report', C.c_float(lr), C.c_float(div), C.c_float(clip), C.c_int64(step), C.byref(c_rep), self._stream())
+        return StepReport(names=names, edges=d_edges, **bufs)
 
     def flat_view(self, which: str) -> torch.Tensor:
         """Zero-copy torch view of the flat fp32 gradient / parameter buffer (for RCCL all-reduce)."""

@@ -54,6 +54,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--restore_step', type=int, default=0, help='restore <train_dir>/model.ckpt-<step> (TF V2 checkpoint) before training / testing; 0 = none when training, '
                    'model.ckpt--1 if present when testing (the reference tests with step -1)')
     p.add_argument('--save_every', type=int, default=0, help='train: write <train_dir>/model.ckpt-<step> every N optimizer steps and at the end (0 = never)')
+    p.add_argument('--step_report', type=int, default=0,
+                   help='train: every N-th optimizer step log the norms of the raw and the clipped gradient, the relative size of the '
+                   'update and the clipped / zero shares (dr_step_report), and stop on a non-finite gradient, naming the variable '
+                   '(0 = never)')
     return p
 
 

@@ -193,7 +193,13 @@ def train(model: JointDetectionModel, dist=None, log=sys.stdout):
     #     window k -- the queue runs one window ahead (the queue-runner role of data/dataset_base.py);
     #   * the losses of window k are READ (the only device -> host synchronisation of the loop) after window k+1 has been queued; the
     #     NaN assert of :147 therefore fires one window late -- one optimizer step has been applied on top of the diverged one, nothing
-    #     is saved in between (the checkpoint of a step is written after its losses were checked).
+    #     is saved in between (the checkpoint of a step is written after its losses were checked);
+    #   * --step_report N: every N-th optimizer step a step report (dr_step_report: the norms, the clipped and zero shares and the
+    #     non-finite count of the gradient that step applies) is queued between the step's gradient reduction and its update; its
+    #     tensors travel with the window's losses and are read with them, so the loop gains no synchronisation point.  A non-finite
+    #     gradient -- which the clip would otherwise turn into an ordinary +-clip step -- stops the run and names the variable.
+    if F.step_report > 0:
+        trainer.report_every(F.step_report, ('global', 'global_counts', 'grad_counts'))
     import queue
     import threading
     todo = queue.Queue(maxsize=2)
@@ -222,7 +228,15 @@ def train(model: JointDetectionModel, dist=None, log=sys.stdout):
 
     def settle(entry):
         """read a finished window's losses: the asserts and the log line of the reference's loop"""
-        st, t0, losses, n_crops = entry
+        st, t0, losses, n_crops, report = entry
+        if report is not None:
+            rstep, rep = report
+            gl, n_bad, n_clip, n_zero = rep.global_.tolist(), *rep.global_counts.tolist()       # (blocks until the report's launches are done)
+            n_el = max(1, int(rep.grad_counts[:, 0].sum()))
+            if log:
+                print('[model/train] step report %d: |a| = %.4g, |g| = %.4g, |u|/|theta| = %.4g, clipped %.4f, zero %.4f'
+                      % (rstep, gl[1], gl[0], gl[3] / gl[2] if gl[2] > 0 else float('nan'), n_clip / n_el, n_zero / n_el), file=log)
+            assert n_bad == 0, 'Model diverged with non-finite gradient in %s' % rep.names[int(torch.nonzero(rep.grad_counts[:, 1])[0])]
         ave_loss = 0.0
         for loss_value in losses.reshape(-1, 4).sum(dim=1).tolist():        # (blocks until that window's launches are done)
             assert not np.isnan(loss_value), 'Model diverged with loss = NaN'          # :147
@@ -263,7 +277,7 @@ def train(model: JointDetectionModel, dist=None, log=sys.stdout):
                 losses = torch.stack(step_losses)
             if pending is not None:
                 settle(pending)                                             # window k-1, while window k runs
-            pending = (step, start, losses, F.batch_size * F.sub_batch)
+            pending = (step, start, losses, F.batch_size * F.sub_batch, trainer.take_step_report() if F.step_report > 0 else None)
             if F.save_every > 0 and ((step + 1) % F.save_every == 0 or step + 1 == max_steps):   # :170-172
                 settle(pending)                                             # a checkpoint is written after ITS losses were checked
                 pending = None

@@ -124,6 +124,7 @@ class DataParallelTrainer:
         eng.forward_train(dm_norm, dropout_mode, keep_mask, rank_seed(seed, self.rank, self.world))
         losses = eng.loss(dm_norm, pose_mm, cfg, com)
         eng.backward(dm_norm.shape[0])
+        self._micro_batch, self._reduced = int(dm_norm.shape[0]), False
         self.micro += 1
         if self.micro % self.sub_batch == 0:
             self.optimizer_step(dm_norm.shape[0])
@@ -165,13 +166,53 @@ class DataParallelTrainer:
             eng.backward(B)
         finally:
             eng.set_groups(1)
+        self._reduced = False
         self.micro += G
         self.optimizer_step(B // G)
         return losses.reshape(G, 4)
 
+    # ---- step report (Engine.step_report): the step the next optimizer_step takes, described before it is taken ----------------
+    _reduced = False            # reduce_gradients already ran for the gradient the flat buffer holds now
+    _micro_batch = None         # crops per micro-step of this rank, as optimizer_step is given them
+    _report_every = 0
+    _report_args = (None, None)
+    _last_report = None
+
+    def step_report(self, fields=None, edges=None):
+        """``Engine.step_report`` with exactly the ``lr``, ``div = sub_batch * world`` and ``step`` the next ``optimizer_step`` will
+        use, after ``reduce_gradients``: under data parallelism it describes the all-reduced gradient (which that
+        ``optimizer_step`` then does not reduce again).  With more than one rank the gradient of an unfinished window cannot be
+        reduced twice, so there the report is taken where the window ends (``report_every``)."""
+        if self._micro_batch is None:
+            raise RuntimeError('step_report: no micro-step has run yet (the learning rate follows its batch size)')
+        if not self._reduced:
+            if self.world > 1 and self.micro % self.sub_batch:
+                raise ValueError('step_report: %d micro-step(s) of an unfinished window are pending; with %d ranks the report is '
+                                 'taken at the end of a window (report_every)' % (self.micro % self.sub_batch, self.world))
+            self.reduce_gradients()
+            self._reduced = True
+        lr = learning_rate(self.global_step, self.dataset, self._micro_batch * self.world, self.sub_batch)
+        return self.eng.step_report(lr, float(self.sub_batch * self.world), self.global_step + 1, GRAD_CLIP, fields=fields, edges=edges)
+
+    def report_every(self, n: int, fields=None, edges=None):
+        """Every ``n``-th ``optimizer_step`` (1-based: steps n, 2n, ...) takes ``step_report(fields, edges)`` between its gradient
+        reduction and its update, with no synchronisation; ``take_step_report`` hands it out.  0 turns it off."""
+        self._report_every = max(0, int(n))
+        self._report_args = (fields, edges)
+
+    def take_step_report(self):
+        """``(step, StepReport)`` of the most recent reported step (device tensors, valid in stream order), once; else ``None``."""
+        rep, self._last_report = self._last_report, None
+        return rep
+
     def optimizer_step(self, batch_size: int):
         """``sess.run(train_op)`` (:150) then ``reset_op`` (:144)."""
-        self.reduce_gradients()
+        self._micro_batch = int(batch_size)
+        if self._report_every and (self.global_step + 1) % self._report_every == 0:
+            self._last_report = (self.global_step + 1, self.step_report(*self._report_args))
+        if not self._reduced:
+            self.reduce_gradients()
+        self._reduced = False
         lr = learning_rate(self.global_step, self.dataset, batch_size * self.world, self.sub_batch)
         self.global_step += 1
         self.eng.apply_adam(lr, float(self.sub_batch * self.world), self.global_step, GRAD_CLIP)

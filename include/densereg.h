@@ -249,6 +249,43 @@ struct dr_loss_report {
 int dr_loss_report(dr_handle* h, int B, const float* dm_norm_dev, const float* pose_mm_dev, const float* cfg_dev,
                    const float* com_dev, const struct dr_loss_report* report, dr_stream stream);
 
+/* ---- step report (training handles) --------------------------------------------------------------- */
+/* Per trainable variable, what the reference histograms (train_single_gpu.py:91-95: every variable and every averaged, clipped
+ * gradient) and what shows a diverging or dead layer before the step is taken.  V = the number of trainable variables in flat
+ * order (dr_param_info with trainable != 0: the layout of dr_flat_param / dr_flat_grad); E = num_edges.  Per element i, with
+ * dr_apply_adam's arithmetic restated op for op:  acc = flat_grad[i] (+ the second micro-step set's accumulator where
+ * dr_sync_grads would add it);  a = acc / div;  g = clip(a, -clip, clip) (a NaN a gives -clip, as in the step);
+ * m' = b1 m + (1-b1) g;  v' = b2 v + (1-b2) g g;  u = lr_t m' / (sqrt(v') + eps): the decrement of theta.
+ * Device pointers, any output member NULL = not wanted; dense, row-major.  min / max ignore NaN (an all-NaN variable gives NaN),
+ * sums propagate it; sums and sums of squares are taken in fp64 in a fixed order and stored as fp32.  Histograms follow numpy:
+ * x falls into bucket searchsorted(edges, x, side='right'), NaN into bucket E.  The struct is read during the call.  (A struct
+ * tag, not a typedef, as dr_vote_report.) */
+struct dr_step_report {
+    const float* hist_edges_dev;  /* in: (E) strictly ascending, finite (the caller's responsibility); NULL iff num_edges == 0 */
+    int32_t      num_edges;       /* in: E, 0..2048 */
+    float*   param_stats_dev;     /* (V,4) min, max, sum, sum of squares of theta */
+    float*   grad_stats_dev;      /* (V,4) the same of g, the clipped averaged gradient the step would apply */
+    float*   raw_stats_dev;       /* (V,2) max |a| and sum a^2 over the FINITE a = acc/div (before the clip); 0, 0 if none */
+    float*   update_stats_dev;    /* (V,4) min, max, sum, sum of squares of u, the decrement the step would apply */
+    int32_t* grad_counts_dev;     /* (V,4) elements; non-finite acc; clipped (a finite and |a| > clip); acc == 0 */
+    float*   global_dev;          /* (6) ||g||2, ||a||2 over finite a, ||theta||2, ||u||2, max|g|, max|u| over all variables */
+    int32_t* global_counts_dev;   /* (3) non-finite, clipped, zero over all variables */
+    int32_t* grad_hist_dev;       /* (V,E+1) bucket counts of g */
+    int32_t* param_hist_dev;      /* (V,E+1) bucket counts of theta */
+};
+/* Describes the step dr_apply_adam(h, lr, div, clip, step, stream) would take if it were called now, and takes none of it.
+ * Needs a training handle (DR_E_STATE otherwise), no forward and no finalised parameters.  Read-only: writes no parameter, no
+ * Adam moment, no gradient accumulator, advances no micro-step, neither folds nor clears the second set's accumulator; it orders
+ * `stream` behind the micro-steps in flight, as dr_sync_grads does, and reads both accumulators.  A step with reports
+ * interleaved ends with the same parameter, m and v bits as one without.  No floating-point atomics: two calls on the same
+ * buffers give the same bits.  Two launches plus the memsets of the histograms, always plain launches (never part of a
+ * DR_GRAPHS=1 graph); members that are NULL cost no loads (without update_stats and global, m and v are not read).  Successive
+ * calls share a workspace and must be ordered by their streams.  DR_E_INVALID: report NULL, no output member set, step < 1, div
+ * or clip not positive, num_edges outside 0..2048, a histogram wanted with num_edges == 0, num_edges > 0 with hist_edges_dev
+ * NULL. */
+int dr_step_report(dr_handle* h, float lr, float div, float clip, int64_t step, const struct dr_step_report* report,
+                   dr_stream stream);
+
 /* ---- dataset formats: PNG depth frames out of the TFRecord files --------------------------- */
 /* Host: undo the PNG row filters (PNG spec 9.2) of an inflated IDAT stream.  `filtered` = height rows of
  * (1 filter-type byte + row_bytes), bpp = bytes per pixel (3 for NYU's RGB8, 2 for 16-bit grey); out = height*row_bytes
