@@ -83,6 +83,16 @@ class DbgBnArgs(C.Structure):
                 ('dres', C.c_void_p), ('fwd_rows', C.c_int), ('bwd_rows', C.c_int)]
 
 
+class DbgBnJoinArgs(C.Structure):
+    """include/densereg_debug.h: dr_dbg_bn_join_args (test hook)."""
+    _fields_ = [(n, C.c_int) for n in ('B', 'H', 'W', 'Cin_s', 'Cin_3', 'Cout', 'groups', 'joined')] + [
+        ('x_s', C.c_void_p), ('xs_cs', C.c_int), ('w_s', C.c_void_p), ('x_3', C.c_void_p), ('x3_cs', C.c_int), ('w_3', C.c_void_p)] + [
+        (n, C.c_void_p) for n in ('gamma_s', 'beta_s', 'mm_s', 'mv_s', 'gamma_3', 'beta_3', 'mm_3', 'mv_3')] + [
+        ('r_max', C.c_float), ('d_max', C.c_float)] + [
+        (n, C.c_void_p) for n in ('dout', 'dst', 'raw_s', 'raw_3', 'draw_s', 'draw_3', 'dgamma_s', 'dbeta_s', 'dgamma_3', 'dbeta_3')] + [
+        ('part_rows', C.c_int)]
+
+
 class DenseRegError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__('densereg error %d: %s' % (code, msg))
@@ -157,6 +167,7 @@ DEBUG_SIGNATURES = {
     'dr_dbg_wgrad': (_i, [_i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, C.c_float, _i, _i, _vp, _vp]),
     'dr_dbg_mfma_peak': (_i, [_i, _i, _i, C.POINTER(C.c_float)]),
     'dr_dbg_bn_layer': (_i, [C.POINTER(DbgBnArgs), _vp]),
+    'dr_dbg_bn_join': (_i, [C.POINTER(DbgBnJoinArgs), _vp]),
     'dr_dbg_maxpool': (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     'dr_dbg_act_dgrad': (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, C.c_float, _vp, _vp, _vp]),
     'dr_dbg_conv2d': (_i, [_i, _i, _i, _i, _i, _i, _fp, _i, _fp, _fp, _fp, _i, _fp, _i, _fp, C.c_float, _fp, _i, _fp, _vp]),

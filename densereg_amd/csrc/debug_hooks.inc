@@ -221,6 +221,146 @@ extern "C" int dr_dbg_bn_layer(dr_dbg_bn_args* a, dr_stream stream) {
     return DR_OK;
 }
 
+// The two BatchReNorm branches of a projection residual (skip conv `s`, last conv `3`; both 1x1 + ReLU), forward and backward,
+// with the executors' launch logic: joined (plan_backward's join_role 1 / 2) or two-pass (densereg_debug.h).
+extern "C" int dr_dbg_bn_join(dr_dbg_bn_join_args* a, dr_stream stream) {
+    if (!a || !a->x_s || !a->w_s || !a->x_3 || !a->w_3 || !a->gamma_s || !a->beta_s || !a->mm_s || !a->mv_s || !a->gamma_3 || !a->beta_3 ||
+        !a->mm_3 || !a->mv_3 || !a->dout || !a->dst || !a->raw_s || !a->raw_3 || !a->draw_s || !a->draw_3 || !a->dgamma_s || !a->dbeta_s ||
+        !a->dgamma_3 || !a->dbeta_3)
+        return DR_E_INVALID;
+    const int G = a->groups > 1 ? a->groups : 1;
+    if (a->B < 1 || a->H < 1 || a->W < 1 || a->Cin_s < 1 || a->Cin_3 < 1 || a->Cout < 1 || a->Cout > 1024 || G > kMaxGroups || a->B % G) return DR_E_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    const int C = a->Cout, cs = dr_round_up(C, 4), Np = dr_round_up(C, 32);
+    const long M = (long)a->B * a->H * a->W, Mg = M / G;
+    const bool joined = a->joined != 0;
+    const size_t n_part = (size_t)std::max<long>((M + 31) / 32, 1024) * 2 * C;
+    std::vector<void*> tmp;
+    auto alloc = [&](size_t bytes) { void* q = rt::dmalloc(std::max<size_t>(bytes, 16)); tmp.push_back(q); return q; };
+    const int Kp_s = dr_round_up(a->Cin_s, 16), Kp_3 = dr_round_up(a->Cin_3, 16);
+    float* wp_s = (float*)alloc((size_t)Kp_s * Np * 4);
+    float* wp_3 = (float*)alloc((size_t)Kp_3 * Np * 4);
+    float* zeros = (float*)alloc(256);
+    // per group: scale | shift of s, scale | shift of 3 (4C), bnc of s, bnc of 3 (8C), coef (3C); once: shadow and next moving state (8C)
+    const long fold_stride = 4l * C, bnc_stride = 8l * C;
+    float* fold = (float*)alloc((size_t)G * 4 * C * 4);
+    float* bnc = (float*)alloc((size_t)G * 8 * C * 4);
+    float* coef = (float*)alloc((size_t)G * 3 * C * 4);
+    float* state = (float*)alloc((size_t)8 * C * 4);
+    double* part = (double*)alloc(n_part * 8);
+    float* skip = (float*)alloc((size_t)M * cs * 4);              // two-pass only: the skip activation and its gradient
+    float* dskip = (float*)alloc((size_t)M * cs * 4);
+    bool ok = true;
+    for (void* q : tmp) ok = ok && q;
+    auto cleanup = [&]() { for (void* q : tmp) if (q) rt::dfree(q); };
+    if (!ok) { cleanup(); return DR_E_NOMEM; }
+    rt::memset_async(zeros, 0, 256, s);
+    rt::memset_async(state, 0, (size_t)8 * C * 4, s);
+    for (float* q : {a->dgamma_s, a->dbeta_s, a->dgamma_3, a->dbeta_3}) rt::memset_async(q, 0, (size_t)C * 4, s);
+    DR_LAUNCH(pack_weights_kernel, dim3(grid_for((long)Kp_s * Np)), dim3(256), 0, s, a->w_s, wp_s, 1, a->Cin_s, C, Kp_s, Np);
+    DR_LAUNCH(pack_weights_kernel, dim3(grid_for((long)Kp_3 * Np)), dim3(256), 0, s, a->w_3, wp_3, 1, a->Cin_3, C, Kp_3, Np);
+    const int rpb = 256 / (cs / 4);
+    const dim3 apply_grid = G > 1 ? dim3(grid_for(Mg, rpb, std::max(bn_grid_cap() / G, 64)), G) : dim3(grid_for(M, rpb, bn_grid_cap()));
+    int rc = 0;
+    // ---- forward: run_conv_train, the skip conv first --------------------------------------------------
+    BnTrainParams fp[2];
+    for (int l = 0; l < 2 && !rc; ++l) {
+        const bool last = l == 1;
+        float* raw = last ? a->raw_3 : a->raw_s;
+        ConvParams p{};
+        p.x = last ? a->x_3 : a->x_s; p.x_cs = last ? a->x3_cs : a->xs_cs; p.Cin = last ? a->Cin_3 : a->Cin_s;
+        p.B = a->B; p.H = a->H; p.W = a->W; p.ksize = 1;
+        p.w = last ? wp_3 : wp_s; p.Kp = last ? Kp_3 : Kp_s; p.Np = Np; p.y = raw; p.y_cs = cs; p.Cout = C; p.stat_part = part; p.zeros = zeros;
+        if (G > 1) p.grp_rows = (int)Mg;
+        // groups that the conv tiles cannot be cut at (the executor rejects such a batch): the statistics rows come from
+        // moments_kernel on the raw output, the executor's path for the stem
+        const bool own_moments = G > 1 && Mg % conv_tile_rows(p) != 0;
+        if (own_moments) p.grp_rows = 0;
+        int part_rows = conv_stat_rows(p);
+        rc = launch_conv_igemm(p, s);
+        if (rc) break;
+        if (own_moments) {
+            const int rows_g = grid_for(std::max<long>(Mg / 8, 1), 1, 1024 / G);
+            part_rows = rows_g * G;
+            DR_LAUNCH(moments_kernel, dim3(rows_g, G), dim3(256), 0, s, (const float*)raw, cs, 0, Mg, C, part);
+        }
+        BnTrainParams& bp = fp[l];
+        bp = BnTrainParams{};
+        bp.raw = raw; bp.raw_cs = cs; bp.M = M; bp.C = C; bp.part = part; bp.part_rows = part_rows;
+        bp.beta = last ? a->beta_3 : a->beta_s; bp.gamma = last ? a->gamma_3 : a->gamma_s;
+        bp.mm = last ? a->mm_3 : a->mm_s; bp.mv = last ? a->mv_3 : a->mv_s;
+        bp.mm_next = state + (last ? 6 : 4) * C; bp.mv_next = state + (last ? 7 : 5) * C;
+        bp.shadow_mean = state + (last ? 2 : 0) * C; bp.shadow_var = state + (last ? 3 : 1) * C; bp.shadow_step = 1;
+        bp.r_max = a->r_max; bp.d_max = a->d_max; bp.eps = 0.001f; bp.decay = 0.99f;
+        for (int g = 0; g < G; ++g) { bp.r_max_g[g] = a->r_max; bp.d_max_g[g] = a->d_max; }
+        bp.groups = G; bp.Mg = Mg; bp.rows_per_group = part_rows / G; bp.fold_stride = fold_stride; bp.bnc_stride = bnc_stride;
+        bp.scale = fold + (last ? 2 : 0) * C; bp.shift = fold + (last ? 3 : 1) * C; bp.bnc = bnc + (last ? 4 : 0) * C; bp.relu = 1;
+        bp.res = View{nullptr, 0, 0, 0};
+        bp.out = last ? View{a->dst, cs, 0, C} : View{skip, cs, 0, C};
+        if (part_rows % G) { rc = -1; break; }
+        if (joined) {
+            launch_bn_fwd_finalize(bp, s);
+            if (last) {
+                BnJoinParams jp{};
+                jp.b = bp; jp.raw2 = a->raw_s; jp.scale2 = fp[0].scale; jp.shift2 = fp[0].shift;
+                DR_LAUNCH(bn_train_join_kernel, apply_grid, dim3(256), 0, s, jp);
+            }
+        } else {
+            if (last) bp.res = View{skip, cs, 0, C};
+            if (G > 1 || bp.part_rows > kBnFuseRows) {
+                launch_bn_fwd_finalize(bp, s);
+                DR_LAUNCH((bn_train_apply_kernel<0, 0>), apply_grid, dim3(256), 0, s, bp);
+            } else {
+                DR_LAUNCH((bn_train_apply_kernel<1, 0>), apply_grid, dim3(256), 0, s, bp);
+            }
+        }
+    }
+    // ---- backward: backward_conv (BatchReNorm part), the last conv first ----------------------------
+    int join_rows = 0;
+    for (int l = 1; l >= 0 && !rc; --l) {
+        const bool last = l == 1;
+        BnBwdParams bp{};
+        bp.dout = (last || joined) ? View{const_cast<float*>(a->dout), cs, 0, C} : View{dskip, cs, 0, C};
+        bp.raw = fp[l].raw; bp.raw_cs = cs; bp.M = M; bp.C = C; bp.relu = 1;
+        bp.scale = fp[l].scale; bp.shift = fp[l].shift; bp.bnc = fp[l].bnc; bp.gamma = fp[l].gamma;
+        bp.part = part; bp.coef = coef;
+        bp.dbeta = last ? a->dbeta_3 : a->dbeta_s; bp.dgamma = last ? a->dgamma_3 : a->dgamma_s;
+        bp.draw = last ? a->draw_3 : a->draw_s;
+        bp.groups = G; bp.Mg = Mg; bp.fold_stride = fold_stride; bp.bnc_stride = bnc_stride;
+        if (last && !joined) { bp.dres = View{dskip, cs, 0, C}; bp.dres_acc = 0; }
+        if (joined && !last) {
+            bp.part_rows = join_rows;
+        } else {
+            const int rows_g = grid_for(Mg, rpb * 8, std::max(256 / G, 32));
+            bp.part_rows = rows_g * G;
+            DR_LAUNCH(bn_bwd_reduce_kernel<0>, dim3(rows_g, G), dim3(256), 0, s, bp);
+        }
+        bp.rows_per_group = bp.part_rows / G;
+        if (joined) {
+            launch_bn_bwd_finalize(bp, s);
+            if (!last) {
+                DR_LAUNCH((bn_bwd_apply_kernel<0, 0>), apply_grid, dim3(256), 0, s, bp);
+            } else {
+                join_rows = (int)(apply_grid.x * apply_grid.y);
+                if ((size_t)join_rows * 2 * C > n_part) { rc = -1; break; }
+                BnBwdJoinParams jp{};
+                jp.b = bp; jp.raw2 = fp[0].raw; jp.scale2 = fp[0].scale; jp.shift2 = fp[0].shift; jp.bnc2 = fp[0].bnc; jp.part2 = part;
+                DR_LAUNCH(bn_bwd_join_kernel, apply_grid, dim3(256), 0, s, jp);
+            }
+        } else if (G > 1 || bp.part_rows > kBnFuseRows) {
+            launch_bn_bwd_finalize(bp, s);
+            DR_LAUNCH((bn_bwd_apply_kernel<0, 0>), apply_grid, dim3(256), 0, s, bp);
+        } else {
+            DR_LAUNCH((bn_bwd_apply_kernel<1, 0>), apply_grid, dim3(256), 0, s, bp);
+        }
+    }
+    a->part_rows = join_rows;
+    rt::sync_stream(s);
+    cleanup();
+    std::string m;
+    if (rc || rt::last_error(&m)) return DR_E_DEVICE;
+    return DR_OK;
+}
 
 extern "C" int dr_dbg_act_dgrad(int B, int H, int W, int C, int Cr, int kr, const float* out, const float* gr, int gr_cs,
                                 const float* wr, float factor, float* g, float* dbias, dr_stream stream) {

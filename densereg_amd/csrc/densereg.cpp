@@ -828,6 +828,7 @@ static void free_all(dr_handle* h) {
 
 namespace {
 int alloc_training_state(dr_handle* h);
+void plan_backward(dr_handle* h);
 }
 
 // ==============================================================================================
@@ -1223,6 +1224,7 @@ int dr_set_precision(dr_handle* h, int precision) {
         h->finalized = false;                                                   // weights must be re-packed
         for (auto& t : h->tensors) t->is_bf16 = false;                          // what a forward stored is void with the old precision
         h->last_forward_train = false;
+        if (h->cfg.training) plan_backward(h);                                  // (the joined projection residuals are fp32 only)
         for (auto& g : h->graphs) rt::graph_destroy(g.g);                       // recorded launches name the old kernels
         h->graphs.clear();
     }
@@ -1753,9 +1755,12 @@ int dr_read_activation(dr_handle* h, const char* scope, int B, float* host, size
             const ConvLayer& c = h->convs[op.conv];
             if (!c.bn || !h->last_forward_train || !c.raw || c.raw->is_bf16) DR_FAIL(h, DR_E_STATE, "dr_read_activation: %s needs a BatchReNorm layer after an fp32 training forward", scope);
             if (part == 2) {
-                if (count != 2 * (size_t)c.cout) DR_FAIL(h, DR_E_INVALID, "dr_read_activation: %s has %d elements, got %zu", scope, 2 * c.cout, count);
+                // (count = groups * 2 * cout: the copies of every micro-batch group, one after the other)
+                const size_t one = 2 * (size_t)c.cout;
+                const size_t ng = (h->groups > 1 && count == one * (size_t)h->groups) ? (size_t)h->groups : 1;
+                if (count != one * ng) DR_FAIL(h, DR_E_INVALID, "dr_read_activation: %s has %d elements, got %zu", scope, 2 * c.cout, count);
                 rt::sync_stream(nullptr);
-                rt::d2h(host, h->fold + c.fold_off, count * sizeof(float), nullptr);
+                for (size_t g = 0; g < ng; ++g) rt::d2h(host + g * one, h->fold + g * h->n_fold + c.fold_off, one * sizeof(float), nullptr);
                 rt::sync_stream(nullptr);
                 DR_CHECK_LAUNCH(h);
                 return DR_OK;
@@ -1780,6 +1785,21 @@ int dr_read_activation(dr_handle* h, const char* scope, int B, float* host, size
         const size_t need = (size_t)M * op.out.C;
         if (count != need) DR_FAIL(h, DR_E_INVALID, "dr_read_activation: %s has %zu elements, got %zu", scope, need, count);
         if (need > h->n_scratch) DR_FAIL(h, DR_E_STATE, "scratch too small");
+        if (h->last_forward_train && op.join_role == 1) {
+            // the skip conv of a joined projection residual: the training forward never wrote this activation (its only reader formed
+            // it on the fly, train_kernels.h: bn_train_join_kernel).  Written now, by the apply pass the two-pass form runs, from the
+            // kept raw output and the coefficients of each micro-batch group.
+            const ConvLayer& c = h->convs[op.conv];
+            const int G = h->groups > 1 ? h->groups : 1;
+            if (B != h->last_B || !c.raw || c.raw->is_bf16) DR_FAIL(h, DR_E_STATE, "dr_read_activation: %s is rebuilt from the last training forward (B=%d)", scope, h->last_B);
+            BnTrainParams bp{};
+            bp.raw = c.raw->p; bp.raw_cs = c.raw->cs; bp.M = M; bp.C = c.cout; bp.relu = c.relu ? 1 : 0;
+            bp.scale = h->fold + c.fold_off; bp.shift = h->fold + c.fold_off + c.cout;
+            bp.res = View{nullptr, 0, 0, 0}; bp.out = op.out.fwd();
+            bp.groups = G; bp.Mg = M / G; bp.fold_stride = (long)h->n_fold; bp.bnc_stride = (long)h->n_bnc;
+            const int rpb = 256 / (c.raw->cs / 4);
+            DR_LAUNCH((bn_train_apply_kernel<0, 0>), dim3(grid_for(bp.Mg, rpb, 512), G), dim3(256), 0, (hipStream_t) nullptr, bp);
+        }
         if (t->is_bf16)                     // stored as bf16 by the training forward of the bf16 path (its only reader is a conv): widen
             DR_LAUNCH(copy_channels_from_bf16_kernel, dim3(grid_for(M * op.out.C)), dim3(256), 0, (hipStream_t) nullptr,
                       reinterpret_cast<const __bf16*>(t->p), t->cs, op.out.coff, h->scratch, op.out.C, 0, M, op.out.C);

@@ -67,6 +67,8 @@ struct ConvLayer {
     Tensor* raw = nullptr;             // pre-BN conv output (training)
     int bst_rows = 0;                  // backward sweep: > 0 = the consumer's dgrad already wrote this many partial rows of
                                        // this layer's BatchReNorm backward sums into stat_part2 (train_exec.inc)
+    int join_rows = 0;                 // backward sweep: > 0 = the joined peer's apply pass wrote this many partial rows of this
+                                       // (skip) layer's backward sums into stat_part (Op::join_role)
     int ep_fwd = 0, ep_bwd = 0;        // launches so far of the look-back apply kernels (targets of the hand-off counters)
     float* g_keep = nullptr;           // small layers (training): a private dRaw buffer that outlives the layer's step of the
                                        // backward sweep, so its weight gradient can run in the grouped launch at the end
@@ -98,6 +100,10 @@ struct Op {
     bool ow_in = false, ow_in2 = false; // backward: this op is the FIRST writer of grad(in) / grad(in2) -> overwrite
     int bst_conv = -1;                 // backward: this conv's dgrad also reduces the BatchReNorm backward sums of conv #bst_conv
     bool bst_last = false;             // ... as the LAST (accumulating) writer of that layer's output gradient rather than the only one
+    // Projection residual, its two BatchReNorm branches joined in one pass (plan_backward; train_kernels.h: bn_train_join_kernel):
+    // join_role 1 = the skip conv (finalize only, no apply pass; its backward sums come from the peer's apply), 2 = the module's
+    // last conv (its apply passes form both branches); join_peer = index in dr_handle::ops of the other one; 0 / -1 = not joined
+    int join_role = 0, join_peer = -1;
 };
 
 enum ParamKind { PK_WEIGHT, PK_BETA, PK_GAMMA, PK_BIAS, PK_MMEAN, PK_MVAR, PK_RMAX, PK_DMAX, PK_CURRT };
@@ -262,6 +268,7 @@ struct dr_handle {
     int* bn_flags = nullptr;                                // [2 counters + 2 expiry flags] per conv: look-back hand-off of the BatchReNorm
                                                             // coefficients (train_kernels.h), opt-in with DR_BN_LOOKBACK=1 (measured slower)
     bool bn_lookback = false;
+    bool bn_join = true;                                    // DR_BN_JOIN=0: projection residuals keep the two-pass path (read when the plan is made)
     bool bf16_act = true;                                   // DR_BF16_ACT=0: single-conv-reader activations stay fp32 on the bf16 path
     bool bf16_draw = true;                                  // DR_BF16_DRAW=0: dRaw stays fp32 on the bf16 matrix-core path (train_exec.inc)
     bool bf16_gact = true;                                  // DR_BF16_GACT=0: the gradient of a single-conv-reader activation stays fp32 on that path

@@ -380,13 +380,42 @@ void plan_backward(dr_handle* h) {
                 t->reader_op = (int)j;
         }
     }
+    // Projection residuals (the graph builder's residual() with num_out != cin: c1, c2, cs, c3 with c3.in2 = cs's output): both
+    // BatchReNorm branches meet in c3's apply passes and the skip activation is never written or differentiated on its own
+    // (train_kernels.h: bn_train_join_kernel, bn_bwd_join_kernel).  fp32 storage and finalize-launch coefficients only;
+    // DR_BN_JOIN=0 keeps the two-pass path (A/B, tests).  Re-planned by dr_set_precision.
+    {
+        const char* e_join = getenv("DR_BN_JOIN");
+        h->bn_join = !(e_join && e_join[0] == '0');
+    }
+    for (Op& op : h->ops) { op.join_role = 0; op.join_peer = -1; }
+    if (h->bn_join && h->precision == 0 && !h->bn_lookback) {
+        for (size_t j = 0; j < h->ops.size(); ++j) {
+            Op& c3 = h->ops[j];
+            if (c3.kind != OP_CONV || !h->convs[c3.conv].bn || !c3.in2.valid()) continue;
+            const Tensor* t = c3.in2.t;
+            if (c3.in2.coff != 0 || c3.in2.C != t->C || readers[t->id] != 1) continue;      // the whole tensor, read by this add only
+            for (size_t i = 0; i < j; ++i) {
+                Op& cs = h->ops[i];
+                if (cs.kind != OP_CONV || cs.out.t != t) continue;
+                const ConvLayer& ls = h->convs[cs.conv];
+                const ConvLayer& l3 = h->convs[c3.conv];
+                if (ls.bn && ls.relu && !cs.in2.valid() && cs.out.coff == 0 && cs.out.C == t->C && cs.lane == c3.lane && cs.join_role == 0 && c3.join_role == 0 &&
+                    ls.cout == l3.cout && ls.H == l3.H && ls.W == l3.W) {
+                    cs.join_role = 1; cs.join_peer = (int)j;
+                    c3.join_role = 2; c3.join_peer = (int)i;
+                }
+            }
+        }
+    }
     if (getenv("DR_DEBUG_PLAN")) {
-        int n_bn = 0, n_only = 0, n_last = 0, n_act = 0;
+        int n_bn = 0, n_only = 0, n_last = 0, n_act = 0, n_join = 0;
+        for (const Op& o : h->ops) n_join += o.join_role == 2 ? 1 : 0;
         for (auto& c : h->convs) n_bn += c.bn ? 1 : 0;
         for (const Op& o : h->ops)
             if (o.bst_conv >= 0) { if (!h->convs[o.bst_conv].bn) ++n_act; else if (o.bst_last) ++n_last; else ++n_only; }
-        fprintf(stderr, "[densereg] plan_backward: %d BatchReNorm layers, sums fused into the only reader's dgrad: %d, into the last writer's: %d; bias convs fused: %d\n",
-                n_bn, n_only, n_last, n_act);
+        fprintf(stderr, "[densereg] plan_backward: %d BatchReNorm layers, sums fused into the only reader's dgrad: %d, into the last writer's: %d; bias convs fused: %d; projection residuals joined: %d\n",
+                n_bn, n_only, n_last, n_act, n_join);
     }
 }
 
@@ -456,7 +485,10 @@ int run_conv_train(dr_handle* h, const Op& op, int B, hipStream_t s) {
         ProfScope ps(h, s, conv_tile_id(p), 2.0 * M * c.k * c.k * c.cin * c.cout, 4.0 * M * ((double)c.cin + c.cout));
         if (launch_conv_igemm(p, s)) DR_FAIL(h, DR_E_STATE, "conv %s: unsupported layout", c.name.c_str());
     }
-    ProfScope ps(h, s, KID_BN, 0.0, 4.0 * M * c.cout * (2.0 + (op.in2.valid() ? 1.0 : 0.0)));
+    // tensor passes of the apply: raw in, activation out (+ the residual in); a joined projection residual (plan_backward) streams
+    // nothing for its skip conv and two raw tensors in, one activation out for its last conv
+    const double bn_passes = op.join_role == 1 ? 0.0 : (2.0 + (op.in2.valid() ? 1.0 : 0.0));
+    ProfScope ps(h, s, KID_BN, 0.0, 4.0 * M * c.cout * bn_passes);
     BnTrainParams bp{};
     bp.raw = raw->p; bp.raw_cs = raw->cs; bp.M = M; bp.C = c.cout; bp.raw_bf16 = raw->is_bf16 ? 1 : 0;
     bp.part = part; bp.part_rows = part_rows;
@@ -498,6 +530,19 @@ int run_conv_train(dr_handle* h, const Op& op, int B, hipStream_t s) {
     }
     if (raw->cs / 4 > 256) DR_FAIL(h, DR_E_UNSUPPORTED, "BatchReNorm layer wider than 1024 channels");
     const int rpb = 256 / (raw->cs / 4);
+    if (op.join_role) {                                      // joined projection residual: always the finalize-launch form
+        if (raw->is_bf16 || bp.out_bf16 || h->precision != 0 || h->bn_lookback) DR_FAIL(h, DR_E_STATE, "conv %s: joined BatchReNorm branches need the fp32 path", c.name.c_str());
+        launch_bn_fwd_finalize(bp, s);
+        if (op.join_role == 1) return DR_OK;                 // the skip conv: coefficients only, the peer's apply forms its activation
+        const ConvLayer& cs = h->convs[h->ops[op.join_peer].conv];
+        if (cs.raw->cs != raw->cs || cs.raw->is_bf16) DR_FAIL(h, DR_E_STATE, "conv %s: joined skip branch with another layout", c.name.c_str());
+        BnJoinParams jp{};
+        jp.b = bp; jp.b.res = View{nullptr, 0, 0, 0};
+        jp.raw2 = cs.raw->p; jp.scale2 = h->fold + cs.fold_off; jp.shift2 = h->fold + cs.fold_off + cs.cout;
+        if (G > 1) DR_LAUNCH(bn_train_join_kernel, dim3(grid_for(Mg, rpb, std::max(bn_grid_cap() / G, 64)), G), dim3(256), 0, s, jp);
+        else DR_LAUNCH(bn_train_join_kernel, dim3(grid_for(M, rpb, bn_grid_cap())), dim3(256), 0, s, jp);
+        return DR_OK;
+    }
     if (G > 1) {                                             // groups: the finalize launch walks the chain, the apply's grid.y = group
         launch_bn_fwd_finalize(bp, s);
         if (bp.raw_bf16) DR_LAUNCH((bn_train_apply_kernel<0, 1>), dim3(grid_for(Mg, rpb, std::max(bn_grid_cap() / G, 64)), G), dim3(256), 0, s, bp);
@@ -600,10 +645,13 @@ int backward_conv(dr_handle* h, const Op& op, int B, hipStream_t s) {
         g16 = conv_tile_id(q) != KID_CONV_SPLITK;
     }
     float* const wg_partial = h->wg_partial_l[op.lane];
-    const View dout = op.out.grad();
-    // residual branch: out = act(...) + res  =>  dres += dout (BatchReNorm layers: inside their backward apply pass)
-    const bool dres_in_bn = c.bn && op.in2.valid() && op.in2.t->needs_grad;
-    if (op.in2.valid() && op.in2.t->needs_grad && !dres_in_bn) {
+    // (a joined skip conv -- plan_backward -- has no gradient buffer of its own to read: d(skip activation) = the module's dOut)
+    const View dout = op.join_role == 1 ? h->ops[op.join_peer].out.grad() : op.out.grad();
+    // residual branch: out = act(...) + res  =>  dres += dout (BatchReNorm layers: inside their backward apply pass; the last conv
+    // of a joined projection residual reduces the skip conv's backward sums there instead and writes no dres)
+    const bool wants_dres = op.in2.valid() && op.in2.t->needs_grad && op.join_role != 2;
+    const bool dres_in_bn = c.bn && wants_dres;
+    if (wants_dres && !dres_in_bn) {
         ProfScope ps(h, s, KID_ELTWISE, 0.0, 12.0 * M * c.cout);
         const View dres = op.in2.grad();
         DR_LAUNCH(copy_channels_kernel, dim3(grid_for(M * c.cout)), dim3(256), 0, s, (const float*)dout.p, dout.cs, dout.coff,
@@ -613,7 +661,10 @@ int backward_conv(dr_handle* h, const Op& op, int B, hipStream_t s) {
     const float* G = nullptr;
     int g_cs = 0, g_coff = 0;
     if (c.bn) {
-        ProfScope ps(h, s, KID_BN, 0.0, 4.0 * M * c.cout * 5.0);
+        // tensor passes: the reduce reads dOut and raw, the apply reads both and writes dRaw; joined projection residual: the skip
+        // conv runs the apply only, the last conv's apply reads the skip conv's raw output as well
+        const double bn_passes = op.join_role == 1 ? 3.0 : op.join_role == 2 ? (c.bst_rows > 0 ? 4.0 : 6.0) : 5.0;
+        ProfScope ps(h, s, KID_BN, 0.0, 4.0 * M * c.cout * bn_passes);
         const float* scale = h->fold + c.fold_off;
         const float* shift = scale + c.cout;
         const float* bnc = h->bnc + c.bnc_off;
@@ -637,7 +688,11 @@ int backward_conv(dr_handle* h, const Op& op, int B, hipStream_t s) {
         const int rpb = 256 / (raw->cs / 4);
         // one partial row per workgroup, folded by finalize; measured (tools/bn_bench.py, [40960][256]): 256 workgroups
         // 22 us, 1024 30 us, 2048 38 us -- one workgroup per CU streams at 3.8 TB/s and keeps the fold short
-        if (c.bst_rows > 0) {                                         // the reader's dgrad already reduced (plan_backward)
+        if (op.join_role == 1) {                                      // the joined peer's apply pass already reduced (plan_backward)
+            if (c.join_rows <= 0) DR_FAIL(h, DR_E_STATE, "conv %s: joined skip branch without its backward sums", c.name.c_str());
+            bp.part_rows = c.join_rows;                               // (in stat_part: the peer's dgrad wrote stat_part2 since)
+            c.join_rows = 0;
+        } else if (c.bst_rows > 0) {                                  // the reader's dgrad already reduced (plan_backward)
             bp.part = h->stat_part2_l[op.lane];
             bp.part_rows = c.bst_rows;
             c.bst_rows = 0;
@@ -649,7 +704,26 @@ int backward_conv(dr_handle* h, const Op& op, int B, hipStream_t s) {
             else DR_LAUNCH(bn_bwd_reduce_kernel<0>, dim3(rows_g, G_), dim3(256), 0, s, bp);
         }
         bp.rows_per_group = bp.part_rows / G_;
-        if (G_ > 1) {
+        if (op.join_role) {                                           // joined projection residual: always the finalize-launch form
+            if (bp.part_rows % G_) DR_FAIL(h, DR_E_STATE, "conv %s: %d backward rows for %d groups", c.name.c_str(), bp.part_rows, G_);
+            if (bp.raw_bf16 || bp.dout_bf16 || bp.draw_bf16 || h->bn_lookback) DR_FAIL(h, DR_E_STATE, "conv %s: joined BatchReNorm branches need the fp32 path", c.name.c_str());
+            launch_bn_bwd_finalize(bp, s);
+            const dim3 grid = G_ > 1 ? dim3(grid_for(Mg, rpb, std::max(bn_grid_cap() / G_, 64)), G_) : dim3(grid_for(M, rpb, bn_grid_cap()));
+            if (op.join_role == 1) {
+                DR_LAUNCH((bn_bwd_apply_kernel<0, 0>), grid, dim3(256), 0, s, bp);
+            } else {
+                ConvLayer& cs = h->convs[h->ops[op.join_peer].conv];
+                const int rows = (int)(grid.x * grid.y);
+                if (cs.raw->cs != raw->cs || cs.raw->is_bf16 || (size_t)rows * 2 * c.cout > h->n_stat_part)
+                    DR_FAIL(h, DR_E_STATE, "conv %s: joined skip branch with another layout, or %d partial rows beyond the buffer", c.name.c_str(), rows);
+                BnBwdJoinParams jp{};
+                jp.b = bp;
+                jp.raw2 = cs.raw->p; jp.scale2 = h->fold + cs.fold_off; jp.shift2 = h->fold + cs.fold_off + cs.cout; jp.bnc2 = h->bnc + cs.bnc_off;
+                jp.part2 = h->stat_part_l[op.lane];                   // (this layer's own rows there, if any, were folded by the finalize above)
+                DR_LAUNCH(bn_bwd_join_kernel, grid, dim3(256), 0, s, jp);
+                cs.join_rows = rows;
+            }
+        } else if (G_ > 1) {
             if (bp.part_rows % G_) DR_FAIL(h, DR_E_STATE, "conv %s: %d backward rows for %d groups", c.name.c_str(), bp.part_rows, G_);
             launch_bn_bwd_finalize(bp, s);
             if (bp.raw_bf16 && bp.dout_bf16) DR_LAUNCH((bn_bwd_apply_kernel<0, 1, 1>), dim3(grid_for(Mg, rpb, std::max(bn_grid_cap() / G_, 64)), G_), dim3(256), 0, s, bp);
@@ -941,7 +1015,7 @@ int backward_impl(dr_handle* h, int B, hipStream_t main_s) {
     if (!h->cfg.training) DR_FAIL(h, DR_E_STATE, "handle was created with training=0");
     if (!h->last_forward_train || B != h->last_B) DR_FAIL(h, DR_E_STATE, "dr_backward needs dr_forward_train + dr_loss with the same B first");
     DR_ENTER(h);
-    for (auto& c : h->convs) c.bst_rows = 0;
+    for (auto& c : h->convs) { c.bst_rows = 0; c.join_rows = 0; }
     for (auto& t : h->tensors) t->g_bf16 = false;             // set again by the input-gradient launches of this sweep
     h->fold_host.clear();
     h->fold_used = h->fold_head;

@@ -495,6 +495,82 @@ __global__ __launch_bounds__(256) void bn_train_apply_kernel(const BnTrainParams
     }
 }
 
+// Projection residual (um_v1.py:18-48 with num_out != cin): out = relu(bn(conv_3)) + relu(bn(conv_skip)).  The skip branch's
+// activation has one reader, this add, and the backward pass rebuilds masks and yhat from `raw`, never from an activation -- so
+// the skip conv runs conv + finalize and NO apply pass, and the last conv's apply forms both terms here: two raw tensors in, one
+// activation out (the two-pass form writes the skip activation and reads it back).  Each term is formed exactly as
+// bn_train_apply_kernel<0, 0> forms it and added where that kernel adds `res`: the output is bit-identical.  fp32 storage,
+// coefficients from finalize launches (MODE 0), blockIdx.y = micro-batch group; b.res is unused.
+struct BnJoinParams {
+    BnTrainParams b;                            // the last conv of the module: raw, scale | shift, relu, out, groups
+    const float* raw2;                          // the skip conv's raw output: same rows, channels and channel stride (b.raw_cs)
+    const float* scale2; const float* shift2;   // its coefficients (group g: b.fold_stride floats behind group g-1's); always ReLU
+};
+__global__ __launch_bounds__(256) void bn_train_join_kernel(const BnJoinParams q) {
+    constexpr int kRows = kBnRows;
+    DR_PIN_ARGS(q.b.raw, q.b.raw_cs, q.b.M, q.b.C, q.b.scale, q.b.shift, q.b.relu, q.raw2, q.scale2, q.shift2, q.b.out.p, q.b.out.cs, q.b.out.coff, (int)gridDim.x);
+    BnTrainParams p = q.b;
+    const float* raw2 = q.raw2;
+    const float* scale2 = q.scale2;
+    const float* shift2 = q.shift2;
+    if (p.groups > 1) {
+        const long g = blockIdx.y, r0 = g * p.Mg;
+        p.raw += r0 * p.raw_cs; raw2 += r0 * p.raw_cs;
+        p.out.p += r0 * p.out.cs;
+        p.scale += g * p.fold_stride; p.shift += g * p.fold_stride;
+        scale2 += g * p.fold_stride; shift2 += g * p.fold_stride;
+        p.M = p.Mg;
+    }
+    const int c4n = p.raw_cs / 4;
+    const int rpb = 256 / c4n;
+    const int cg = threadIdx.x % c4n, rp = threadIdx.x / c4n;
+    if (rp >= rpb) return;
+    float sc[4], sh[4], sc2[4], sh2[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int c = cg * 4 + k, cc = c < p.C ? c : p.C - 1;       // unconditional loads, see bn_train_apply_kernel
+        sc[k] = p.scale[cc]; sh[k] = p.shift[cc];
+        sc2[k] = scale2[cc]; sh2[k] = shift2[cc];
+    }
+    const bool full = cg * 4 + 4 <= p.C;
+    const bool vec_out = full && (p.out.coff % 4 == 0) && (p.out.cs % 4 == 0);
+    const long stride = (long)gridDim.x * rpb;
+    for (long m0 = (long)blockIdx.x * rpb + rp; m0 < p.M; m0 += stride * kRows) {
+        float4 x[kRows], y[kRows];
+#pragma unroll
+        for (int u = 0; u < kRows; ++u) {
+            const long m = m0 + u * stride, mc = m < p.M ? m : p.M - 1;     // tail rows re-read the last row
+            x[u] = bn_ld4(p.raw + mc * p.raw_cs + cg * 4);
+        }
+#pragma unroll
+        for (int u = 0; u < kRows; ++u) {
+            const long m = m0 + u * stride, mc = m < p.M ? m : p.M - 1;
+            y[u] = bn_ld4(raw2 + mc * p.raw_cs + cg * 4);
+        }
+#pragma unroll
+        for (int u = 0; u < kRows; ++u) {
+            const long m = m0 + u * stride;
+            if (m >= p.M) break;
+            float v[4] = {x[u].x * sc[0] + sh[0], x[u].y * sc[1] + sh[1], x[u].z * sc[2] + sh[2], x[u].w * sc[3] + sh[3]};
+            float w[4] = {y[u].x * sc2[0] + sh2[0], y[u].y * sc2[1] + sh2[1], y[u].z * sc2[2] + sh2[2], y[u].w * sc2[3] + sh2[3]};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (p.relu) v[k] = fmaxf(v[k], 0.f);
+                w[k] = fmaxf(w[k], 0.f);                                    // what the skip conv's own apply pass would have stored
+                v[k] += w[k];
+            }
+            float* o = p.out.p + m * p.out.cs + p.out.coff + cg * 4;
+            if (vec_out) {
+                bn_st4(o, make_float4(v[0], v[1], v[2], v[3]));
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (cg * 4 + k < p.C) o[k] = v[k];
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // BatchReNorm backward.
 //   out = gamma*(r*yhat + d) + beta, yhat = (x-mean)*inv_std, g = dOut * [out_pre_relu > 0]
@@ -799,6 +875,123 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BnBwdParams p_i
                 bn_st4h(reinterpret_cast<__bf16*>(p.draw) + m * p.raw_cs + cg * 4, __builtin_convertvector(f, dr_bf16x4));
             } else {
                 bn_st4(p.draw + m * p.raw_cs + cg * 4, make_float4(o[0], o[1], o[2], o[3]));
+            }
+        }
+    }
+}
+
+// Backward of the joined projection residual (bn_train_join_kernel): the last conv's apply pass.  d(skip activation) = dOut, so
+// instead of copying dOut into a gradient buffer of the skip activation (and the skip conv reading it back in a reduce pass of
+// its own) this pass also loads the skip conv's raw output and reduces ITS backward sums -- sum g2, sum g2 * yhat2 with
+// g2 = dOut * [raw2 * scale2 + shift2 > 0] -- into one fp64 partial row per workgroup, bn_bwd_reduce_kernel's layout and fixed
+// in-block order (rows of group g behind those of group g-1; no floating-point atomics).  The skip conv then runs finalize on
+// those rows and an apply pass that reads dOut from this layer's output gradient.  fp32 storage, MODE 0 coefficients,
+// blockIdx.y = micro-batch group; b.dres is unused.
+struct BnBwdJoinParams {
+    BnBwdParams b;                              // the last conv of the module: dout, raw, coefficients, draw
+    const float* raw2;                          // the skip conv's raw output (channel stride b.raw_cs)
+    const float* scale2; const float* shift2; const float* bnc2;   // its forward values (groups: fold_stride / bnc_stride apart)
+    double* part2;                              // out: [2][C][gridDim.x * gridDim.y] partial rows of the skip conv's sums
+};
+__global__ __launch_bounds__(256) void bn_bwd_join_kernel(const BnBwdJoinParams q) {
+    constexpr int kRows = kBnRows;
+    DR_PIN_ARGS(q.b.dout.p, q.b.dout.cs, q.b.dout.coff, q.b.raw, q.b.raw_cs, q.b.M, q.b.C, q.b.relu, q.b.scale, q.b.shift, q.b.bnc, q.b.coef, q.b.draw, q.raw2, q.scale2, q.shift2, q.bnc2, q.part2, (int)gridDim.x);
+    BnBwdParams p = q.b;
+    const float* raw2 = q.raw2;
+    const float* scale2 = q.scale2;
+    const float* shift2 = q.shift2;
+    const float* bnc2 = q.bnc2;
+    int part_row = (int)blockIdx.x, part_rows = (int)gridDim.x;
+    if (p.groups > 1) {
+        const long g = blockIdx.y, r0 = g * p.Mg;
+        p.dout.p += r0 * p.dout.cs;
+        p.raw += r0 * p.raw_cs; raw2 += r0 * p.raw_cs;
+        p.draw += r0 * p.raw_cs;
+        p.scale += g * p.fold_stride; p.shift += g * p.fold_stride; p.bnc += g * p.bnc_stride; p.coef += g * 3 * p.C;
+        scale2 += g * p.fold_stride; shift2 += g * p.fold_stride; bnc2 += g * p.bnc_stride;
+        p.M = p.Mg;
+        part_row += (int)g * (int)gridDim.x; part_rows *= (int)gridDim.y;
+    }
+    __shared__ double s1[256 * 4];
+    __shared__ double s2[256 * 4];
+    const int c4n = p.raw_cs / 4;
+    const int rpb = 256 / c4n;
+    const int tid = threadIdx.x;
+    const int cg = tid % c4n, rp = tid / c4n;
+    double a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
+    if (rp < rpb) {
+        float sc[4], sh[4], mean[4], istd[4], c1[4], c2[4], c3[4], sc2[4], sh2[4], mean2[4], istd2[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int c = cg * 4 + k, cc = c < p.C ? c : p.C - 1;          // unconditional loads, see bn_train_apply_kernel
+            sc[k] = p.scale[cc]; sh[k] = p.shift[cc]; mean[k] = p.bnc[cc]; istd[k] = p.bnc[p.C + cc];
+            c1[k] = p.coef[cc]; c2[k] = p.coef[p.C + cc]; c3[k] = p.coef[2 * p.C + cc];
+            sc2[k] = scale2[cc]; sh2[k] = shift2[cc]; mean2[k] = bnc2[cc]; istd2[k] = bnc2[p.C + cc];
+        }
+        const bool full = cg * 4 + 4 <= p.C;
+        const bool vec_d = full && (p.dout.coff % 4 == 0) && (p.dout.cs % 4 == 0);
+        const long stride = (long)gridDim.x * rpb;
+        for (long m0 = (long)blockIdx.x * rpb + rp; m0 < p.M; m0 += stride * kRows) {
+            float4 x4[kRows], y4[kRows], d4[kRows];
+#pragma unroll
+            for (int u = 0; u < kRows; ++u) {
+                const long m = m0 + u * stride, mc = m < p.M ? m : p.M - 1;
+                x4[u] = bn_ld4(p.raw + mc * p.raw_cs + cg * 4);
+            }
+#pragma unroll
+            for (int u = 0; u < kRows; ++u) {
+                const long m = m0 + u * stride, mc = m < p.M ? m : p.M - 1;
+                y4[u] = bn_ld4(raw2 + mc * p.raw_cs + cg * 4);
+            }
+            if (vec_d) {
+#pragma unroll
+                for (int u = 0; u < kRows; ++u) {
+                    const long m = m0 + u * stride, mc = m < p.M ? m : p.M - 1;
+                    d4[u] = bn_ld4(p.dout.p + mc * p.dout.cs + p.dout.coff + cg * 4);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < kRows; ++u) {
+                const long m = m0 + u * stride;
+                if (m >= p.M) break;
+                const float x[4] = {x4[u].x, x4[u].y, x4[u].z, x4[u].w};
+                const float y[4] = {y4[u].x, y4[u].y, y4[u].z, y4[u].w};
+                float g[4] = {0.f, 0.f, 0.f, 0.f};
+                if (vec_d) {
+                    g[0] = d4[u].x; g[1] = d4[u].y; g[2] = d4[u].z; g[3] = d4[u].w;
+                } else {
+                    const float* dp = p.dout.p + m * p.dout.cs + p.dout.coff + cg * 4;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (cg * 4 + k < p.C) g[k] = dp[k];
+                }
+                float o[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float g2 = (y[k] * sc2[k] + sh2[k] > 0.f) ? g[k] : 0.f;       // the skip branch: always ReLU
+                    const float yh2 = (y[k] - mean2[k]) * istd2[k];
+                    a[k] += (double)g2;
+                    b[k] += (double)g2 * (double)yh2;
+                    if (p.relu && !(x[k] * sc[k] + sh[k] > 0.f)) g[k] = 0.f;
+                    const float yh = (x[k] - mean[k]) * istd[k];
+                    o[k] = (cg * 4 + k < p.C) ? c1[k] * (g[k] - c2[k] - yh * c3[k]) : 0.f;
+                }
+                bn_st4(p.draw + m * p.raw_cs + cg * 4, make_float4(o[0], o[1], o[2], o[3]));
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { s1[tid * 4 + k] = a[k]; s2[tid * 4 + k] = b[k]; }
+    __syncthreads();
+    if (tid < c4n) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int c = tid * 4 + k;
+            if (c < p.C) {
+                double ta = 0.0, tb = 0.0;
+                for (int r = 0; r < rpb; ++r) { ta += s1[(r * c4n + tid) * 4 + k]; tb += s2[(r * c4n + tid) * 4 + k]; }
+                q.part2[(long)c * part_rows + part_row] = ta;                      // [2][C][rows]
+                q.part2[((long)p.C + c) * part_rows + part_row] = tb;
             }
         }
     }

@@ -63,6 +63,31 @@ typedef struct dr_dbg_bn_args {
 } dr_dbg_bn_args;
 int dr_dbg_bn_layer(dr_dbg_bn_args* a, dr_stream stream);
 
+/* The two BatchReNorm branches of a PROJECTION RESIDUAL (um_v1.py:18-48 with num_out != cin), forward and backward, through the
+ * kernels and the launch logic of the executors: the skip conv `s` (1x1, Cin_s -> Cout, BatchReNorm + ReLU) and the module's last
+ * conv `3` (1x1, Cin_3 -> Cout, BatchReNorm + ReLU), dst = relu(bn(conv_3)) + relu(bn(conv_s)), then the backward from `dout`.
+ * joined = 1: the skip conv runs conv + statistics + finalize only, the last conv's apply passes form both branches (the
+ * executors' default on the fp32 path); joined = 0: the two-pass form (DR_BN_JOIN=0) -- the skip activation is written, read back
+ * as the residual, its gradient copied and reduced by a pass of its own.  groups > 1: micro-batch groups (dr_set_groups), B a
+ * multiple of it; statistics, r / d and the moving-state chain per group.  Tensors are NHWC, channel stride round_up(Cout, 4)
+ * unless a stride is given; moving statistics start the zero-debiased chain (first update).  All pointers are device pointers;
+ * synchronises the stream. */
+typedef struct dr_dbg_bn_join_args {
+    int B, H, W, Cin_s, Cin_3, Cout, groups, joined;
+    const float* x_s; int xs_cs; const float* w_s;           /* skip conv: input, its channel stride, HWIO (1,1,Cin_s,Cout) */
+    const float* x_3; int x3_cs; const float* w_3;           /* last conv */
+    const float* gamma_s; const float* beta_s; const float* mm_s; const float* mv_s;      /* [Cout] each */
+    const float* gamma_3; const float* beta_3; const float* mm_3; const float* mv_3;
+    float r_max, d_max;
+    const float* dout;                                       /* [M][cs]: gradient wrt dst */
+    float* dst;                                              /* out [M][cs] */
+    float* raw_s; float* raw_3;                              /* out [M][cs]: raw conv outputs */
+    float* draw_s; float* draw_3;                            /* out [M][cs]: gradients wrt the raw conv outputs */
+    float* dgamma_s; float* dbeta_s; float* dgamma_3; float* dbeta_3;                     /* out [Cout] */
+    int part_rows;                                           /* out: partial rows the joined backward apply wrote (0: two-pass) */
+} dr_dbg_bn_join_args;
+int dr_dbg_bn_join(dr_dbg_bn_join_args* a, dr_stream stream);
+
 /* The backward of a BIAS conv with ReLU (and dropout) as its single reader's dgrad produces it (conv_igemm.h, bst_act):
  * `out` [M][cs] is the layer's forward output, the reader is a kr x kr conv C -> Cr with output gradient `gr`; writes
  * g [M][cs] = dOut * factor * [out > 0] (dOut = the reader's input gradient) and dbias[C] += column sums of g. */
