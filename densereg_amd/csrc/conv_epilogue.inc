@@ -144,14 +144,14 @@
                             // a bf16-stored dOut (below): the sums are taken over the value the producer's apply pass will read back
                             if (EP_B16 && EP_B16_CONST && p.y_bf16) v = (float)(__bf16)v;
                             float g = v;
-                            if (p.bst_relu && !(braw[q] * b_sc + b_sh > 0.f)) g = 0.f;
+                            if (p.bst_relu && !(bn_affine(braw[q], b_sc, b_sh) > 0.f)) g = 0.f;
                             g *= b_fac;
                             if (p.bst_act) v = g;                          // the producer reads its dRaw straight from here
                             // (the copy that reads a bf16 raw output: dOut of a tensor this launch is the ONLY writer of may be stored
                             // as bf16 too -- its one reader is the producer's backward apply pass, train_exec.inc)
                             if (EP_B16 && EP_B16_CONST && p.y_bf16) reinterpret_cast<__bf16*>(p.y)[m * (unsigned)p.y_cs + (unsigned)(p.y_coff + n)] = (__bf16)v;
                             else DR_NT_STORE(4, &p.y[m * (unsigned)p.y_cs + (unsigned)(p.y_coff + n)], v);
-                            const float yh = (braw[q] - b_mean) * b_istd;
+                            const float yh = bn_yhat(braw[q], b_mean, b_istd);
                             s1[j] += (double)g;
                             s2[j] += (double)g * (double)yh;
                         } else {

@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "dr_platform.h"
+#include "bn_math.h"
 
 namespace dr {
 

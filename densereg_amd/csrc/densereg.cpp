@@ -1618,6 +1618,15 @@ static int infer_launches(dr_handle* h, int B, const float* dm, const float* cfg
     return vote_impl(h, B, a.fwd(), b.fwd(), c.fwd(), h->tiny, cfg, com, xyz, s, report);
 }
 
+// The three heads of every stack as views: the predictions and, for dr_loss, the gradient seeds behind them.
+static void stack_maps(dr_handle* h, StackMaps& pred, StackMaps* seed) {
+    for (int i = 0; i < h->cfg.num_stack; ++i) {
+        TView a{h->hm[i], 0, h->hm[i]->C}, b{h->hm3[i], 0, h->hm3[i]->C}, c{h->um[i], 0, h->um[i]->C};
+        pred.hm[i] = a.fwd(); pred.hm3[i] = b.fwd(); pred.um[i] = c.fwd();
+        if (seed) { seed->hm[i] = a.grad(); seed->hm3[i] = b.grad(); seed->um[i] = c.grad(); }
+    }
+}
+
 // dr_targets / dr_loss_report (loss_report.h): one launch for the targets; when a loss member is wanted the same launch also leaves
 // fp64 partial sums per (crop, chunk, stack, joint, term), which two small launches add up in a fixed order.  Reads the maps of the
 // bound slot and writes nothing the handle owns but the report's workspace.  Accounted under the loss's kernel id.
@@ -1644,10 +1653,7 @@ static int loss_report_launches(dr_handle* h, int B, const float* dm, const floa
     double* part = h->loss_report_ws;
     double* bsj = part + MB * nchunk * n;
     double* cropd = bsj + MB * n;
-    for (int i = 0; i < lp.S; ++i) {
-        TView a{h->hm[i], 0, h->hm[i]->C}, b{h->hm3[i], 0, h->hm3[i]->C}, c{h->um[i], 0, h->um[i]->C};
-        lp.hm[i] = a.fwd(); lp.hm3[i] = b.fwd(); lp.um[i] = c.fwd();
-    }
+    stack_maps(h, lp.pred, nullptr);
     lp.part = part;
     if (h->pipe_depth == 2 && h->slot[h->cur_slot].fwd_recorded) rt::stream_wait_event(s, h->slot[h->cur_slot].fwd_done);
     ProfScope ps(h, s, KID_LOSS, 0.0, 4.0 * B * npix * lp.S * 5.0 * lp.J + map_bytes + 4.0 * B * npix);

@@ -9,6 +9,7 @@
 //   moments_kernel       per-channel sum / sum of squares (tf.nn.moments, ops.py:132)
 #pragma once
 #include "dr_platform.h"
+#include "pose_math.h"
 
 namespace dr {
 
@@ -202,11 +203,11 @@ __global__ __launch_bounds__(256) void norm_dm_kernel(const float* dm, const flo
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int b = int(i / npix);
         const float cz = com[b * 3 + 2];
-        const float max_depth = cz + 300.0f * 0.5f;
-        const float min_depth = cz - 300.0f * 0.5f;
+        const float max_depth = cz + kDepthRange * 0.5f;
+        const float min_depth = cz - kDepthRange * 0.5f;
         const float d = dm[i];
-        const bool m = (d < max_depth) && (d > (min_depth - 300.0f * 0.5f));
-        out[i] = m ? (d - min_depth) / 300.0f : -1.0f;
+        const bool m = (d < max_depth) && (d > (min_depth - kDepthRange * 0.5f));
+        out[i] = m ? (d - min_depth) / kDepthRange : -1.0f;
     }
 }
 

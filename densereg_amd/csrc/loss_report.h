@@ -5,15 +5,15 @@
 //   loss_report_kernel    loss_report_body<true>:  the same, plus per-workgroup fp64 partial sums of every stack's loss terms
 //   loss_report_crop_kernel / loss_report_out_kernel   the partials summed in a fixed order into the report's members
 //
-// Read-only with respect to the handle: no gradient seed, no accumulator.  The target arithmetic is loss_kernel's (train_kernels.h)
-// restated op for op in fp32 with contraction off; loss_kernel itself is untouched (tests/test_loss_report.py ties the two together).
+// Read-only with respect to the handle: no gradient seed, no accumulator.  The targets are pose_math.h's (map_cam, cloud_point,
+// pose_targets): the functions loss_kernel (train_kernels.h) calls, so the two cannot drift apart.
 #pragma once
 #include "train_kernels.h"
 
 namespace dr {
 
 struct LossReportParams {
-    View hm[kMaxStack], hm3[kMaxStack], um[kMaxStack];        // predictions of the most recent forward (sums only)
+    StackMaps pred;                                           // predictions of the most recent forward (sums only)
     int S, B, h, w, J, in_hw;
     const float* dm; const float* pose; const float* cfg; const float* com;   // dm: the normalised crop at input resolution
     float* gt_hm; float* gt_hm3; float* gt_um;                // (B,h,w,J) (B,h,w,J) (B,h,w,3J); any may be NULL
@@ -34,46 +34,20 @@ __device__ __forceinline__ void loss_report_body(const LossReportParams& p) {
     const bool live = e < npix * p.J;
     int j = 0;
     long m = 0;
-    float gt_hm = 0.f, gt_hm3 = 0.f, ux = 0.f, uy = 0.f, uz = 0.f;
+    PoseTargets gt{};
     if (live) {
         j = e % p.J;
         const int px = e / p.J;
         m = (long)b * npix + px;
-        const float* cfg = p.cfg + b * 6;
-        const float cx0 = p.com[b * 3 + 0], cy0 = p.com[b * 3 + 1], cz0 = p.com[b * 3 + 2];
-        const float w_ratio = cfg[4] / (float)p.w, h_ratio = cfg[5] / (float)p.h;
-        const float fx = cfg[0] / w_ratio, fy = cfg[1] / h_ratio, cx = cfg[2] / w_ratio, cy = cfg[3] / h_ratio;
-        const int ix = px % p.w, iy = px / p.w;
-        const float xx = (float)ix, yy = (float)iy;
-        // point cloud at this pixel (preprocess.py:202-225); the depth at the map's stride straight from the crop (tiny_dm = [::4, ::4]):
-        // no forward's copy of it is needed
-        const int st = p.in_hw / p.w;
+        // the depth at the map's stride straight from the crop (tiny_dm = [::4, ::4]): no forward's copy of it is needed
+        const int ix = px % p.w, iy = px / p.w, st = p.in_hw / p.w;
         const float t = p.dm[((long)b * p.in_hw + iy * st) * p.in_hw + ix * st];
-        const float min_depth = cz0 - 300.0f * 0.5f, max_depth = cz0 + 300.0f * 0.5f;
-        const float zz = (t < -0.99f) ? max_depth : (t * 300.0f + min_depth);
-        float X = (xx - cx) * (zz / fx);
-        float Y = (yy - cy) * (zz / fy);
-        X = (X - cx0) / 100.0f;
-        Y = (Y - cy0) / 100.0f;
-        const float Z = (zz - cz0) / 100.0f;
-        const float* ps = p.pose + (long)b * 3 * p.J + 3 * j;
-        // 2D cone (:225-242)
-        const float u = ps[0] * fx / ps[2] + cx;
-        const float v = ps[1] * fy / ps[2] + cy;
-        const float du = xx - u, dv = yy - v;
-        gt_hm = fmaxf(4.0f - sqrtf(du * du + dv * dv), 0.0f) / 4.0f;
-        // 3D offsets (:338-346)
-        const float ox = (ps[0] - cx0) / 100.0f - X;
-        const float oy = (ps[1] - cy0) / 100.0f - Y;
-        const float oz = (ps[2] - cz0) / 100.0f - Z;
-        const float dist = sqrtf((ox * ox + oy * oy) + oz * oz);
-        gt_hm3 = fmaxf((0.8f - dist) / 0.8f, 0.0f);
-        const float d3 = 0.8f - gt_hm3 * 0.8f;
-        const bool near = d3 < (0.8f - 1e-2f);
-        ux = near ? ox / d3 : 0.0f; uy = near ? oy / d3 : 0.0f; uz = near ? oz / d3 : 0.0f;
-        if (p.gt_hm) p.gt_hm[m * p.J + j] = gt_hm;
-        if (p.gt_hm3) p.gt_hm3[m * p.J + j] = gt_hm3;
-        if (p.gt_um) { float* q = p.gt_um + m * 3 * p.J + 3 * j; q[0] = ux; q[1] = uy; q[2] = uz; }
+        const MapCam cam = map_cam(p.cfg + b * 6, p.w, p.h);
+        const CloudPoint cloud = cloud_point(cam, p.com + b * 3, t, px, p.w);
+        gt = pose_targets(cam, p.com + b * 3, p.pose + (long)b * 3 * p.J + 3 * j, cloud, px, p.w);
+        if (p.gt_hm) p.gt_hm[m * p.J + j] = gt.gt_hm;
+        if (p.gt_hm3) p.gt_hm3[m * p.J + j] = gt.gt_hm3;
+        if (p.gt_um) { float* q = p.gt_um + m * 3 * p.J + 3 * j; q[0] = gt.ux; q[1] = gt.uy; q[2] = gt.uz; }
     }
     if constexpr (SUMS) {
         // Deterministic fp64 sums without atomics: stack by stack (a per-thread array over the stacks would live in scratch), the
@@ -86,10 +60,10 @@ __device__ __forceinline__ void loss_report_body(const LossReportParams& p) {
         double* part = p.part + ((long)b * gridDim.x + blockIdx.x) * p.S * p.J * 3;
         for (int s = 0; s < p.S; ++s) {
             if (live) {
-                const float e1 = p.hm[s].p[m * p.hm[s].cs + p.hm[s].coff + j] - gt_hm;
-                const float e2 = p.hm3[s].p[m * p.hm3[s].cs + p.hm3[s].coff + j] - gt_hm3;
-                const float* um = p.um[s].p + m * p.um[s].cs + p.um[s].coff + 3 * j;
-                const float e3 = um[0] - ux, e4 = um[1] - uy, e5 = um[2] - uz;
+                const float e1 = p.pred.hm[s].p[m * p.pred.hm[s].cs + p.pred.hm[s].coff + j] - gt.gt_hm;
+                const float e2 = p.pred.hm3[s].p[m * p.pred.hm3[s].cs + p.pred.hm3[s].coff + j] - gt.gt_hm3;
+                const float* um = p.pred.um[s].p + m * p.pred.um[s].cs + p.pred.um[s].coff + 3 * j;
+                const float e3 = um[0] - gt.ux, e4 = um[1] - gt.uy, e5 = um[2] - gt.uz;
                 term[0][threadIdx.x] = 0.5 * (double)e1 * e1;
                 term[1][threadIdx.x] = 0.5 * (double)e2 * e2;
                 term[2][threadIdx.x] = 0.5 * ((double)e3 * e3 + (double)e4 * e4 + (double)e5 * e5);

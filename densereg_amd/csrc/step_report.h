@@ -7,10 +7,9 @@
 //   step_report_fold_kernel    one workgroup per variable: its chunks folded in a fixed order into the per-variable members; one
 //                              more workgroup: all chunks folded in a fixed order into the global members
 //
-// Read-only: nothing the handle owns is written but the report's workspace.  The per-element arithmetic is adam_kernel's
-// (train_kernels.h) RESTATED op for op in fp32 with contraction off -- adam_kernel itself is untouched, so no helper is shared --
-// and, where the second micro-step slot holds gradients, grad_merge_kernel's one addition in front of it
-// (tests/test_step_report.py ties the restatement to the step dr_apply_adam takes, bit for bit).  No floating-point atomics:
+// Read-only: nothing the handle owns is written but the report's workspace.  The per-element arithmetic is adam_elem
+// (train_kernels.h), the function adam_kernel applies, and, where the second micro-step slot holds gradients, grad_merge_kernel's
+// one addition in front of it (tests/test_step_report.py holds it to the step dr_apply_adam takes, bit for bit).  No floating-point atomics:
 // every sum is fp64 in an order fixed by the chunk table alone.
 #pragma once
 #include "train_kernels.h"
@@ -57,7 +56,7 @@ __device__ __forceinline__ int step_bucket(const float* edges, int E, float x) {
 // and the four elements of a 16-byte group could not be scheduled together.
 enum { kStepParam = 1, kStepGrad = 2, kStepUpd = 4, kStepHist = 8 };
 
-// One element.  Everything from `a` to `u` is adam_kernel's arithmetic, restated.
+// One element.  Everything from `a` to `u` comes from adam_elem.
 template <int MODE>
 __device__ __forceinline__ void step_elem(const StepReportParams& p, StepAcc& A, float th, float acc, float mi0, float vi0,
                                           const float* edges, int* hg, int* hp) {
@@ -70,8 +69,8 @@ __device__ __forceinline__ void step_elem(const StepReportParams& p, StepAcc& A,
         if constexpr ((MODE & kStepHist) != 0) { if (hp) atomicAdd(&hp[step_bucket(edges, p.E, th)], 1); }
     }
     if constexpr ((MODE & kStepGrad) != 0) {
-        const float a = acc / p.div;
-        const float g = fminf(fmaxf(a, -p.clip), p.clip);
+        const AdamElem e = adam_elem(acc, mi0, vi0, p.div, p.clip, p.lr_t, p.b1, p.b2, p.eps);
+        const float a = e.a, g = e.g;
         A.s[2] += (double)g;
         A.s[3] += (double)g * (double)g;
         A.mm[2] = fminf(A.mm[2], g);
@@ -85,13 +84,10 @@ __device__ __forceinline__ void step_elem(const StepReportParams& p, StepAcc& A,
         A.cnt[2] += acc == 0.f ? 1 : 0;
         if constexpr ((MODE & kStepHist) != 0) { if (hg) atomicAdd(&hg[step_bucket(edges, p.E, g)], 1); }
         if constexpr ((MODE & kStepUpd) != 0) {
-            const float mi = p.b1 * mi0 + (1.0f - p.b1) * g;
-            const float vi = p.b2 * vi0 + (1.0f - p.b2) * g * g;
-            const float u = p.lr_t * mi / (sqrtf(vi) + p.eps);
-            A.s[5] += (double)u;
-            A.s[6] += (double)u * (double)u;
-            A.mm[5] = fminf(A.mm[5], u);
-            A.mm[6] = fmaxf(A.mm[6], u);
+            A.s[5] += (double)e.u;
+            A.s[6] += (double)e.u * (double)e.u;
+            A.mm[5] = fminf(A.mm[5], e.u);
+            A.mm[6] = fmaxf(A.mm[6], e.u);
         }
     }
 }

@@ -1216,11 +1216,7 @@ int dr_loss(dr_handle* h, int B, const float* dm, const float* pose, const float
     }
     LossParams lp{};
     lp.S = h->cfg.num_stack; lp.B = B; lp.h = h->map_hw; lp.w = h->map_hw; lp.J = h->cfg.num_jnt;
-    for (int i = 0; i < lp.S; ++i) {
-        TView a{h->hm[i], 0, h->hm[i]->C}, b{h->hm3[i], 0, h->hm3[i]->C}, c{h->um[i], 0, h->um[i]->C};
-        lp.hm[i] = a.fwd(); lp.hm3[i] = b.fwd(); lp.um[i] = c.fwd();
-        lp.dhm[i] = a.grad(); lp.dhm3[i] = b.grad(); lp.dum[i] = c.grad();
-    }
+    stack_maps(h, lp.pred, &lp.seed);
     lp.tiny = h->tiny; lp.pose = pose; lp.cfg = cfg; lp.com = com; lp.acc = h->loss_acc;
     {
         ProfScope ps(h, s, KID_LOSS, 0.0, 4.0 * B * lp.h * lp.w * lp.S * 10.0 * lp.J);

@@ -9,6 +9,8 @@
 #pragma once
 #include "dr_platform.h"
 #include "kernels_misc.h"
+#include "bn_math.h"
+#include "pose_math.h"
 
 namespace dr {
 
@@ -467,7 +469,7 @@ __global__ __launch_bounds__(256) void bn_train_apply_kernel(const BnTrainParams
         for (int u = 0; u < kRows; ++u) {
             const long m = m0 + u * stride;
             if (m >= p.M) break;
-            float v[4] = {x[u].x * sc[0] + sh[0], x[u].y * sc[1] + sh[1], x[u].z * sc[2] + sh[2], x[u].w * sc[3] + sh[3]};
+            float v[4] = {bn_affine(x[u].x, sc[0], sh[0]), bn_affine(x[u].y, sc[1], sh[1]), bn_affine(x[u].z, sc[2], sh[2]), bn_affine(x[u].w, sc[3], sh[3])};
             if (p.relu) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) v[k] = fmaxf(v[k], 0.f);
@@ -498,8 +500,8 @@ __global__ __launch_bounds__(256) void bn_train_apply_kernel(const BnTrainParams
 // Projection residual (um_v1.py:18-48 with num_out != cin): out = relu(bn(conv_3)) + relu(bn(conv_skip)).  The skip branch's
 // activation has one reader, this add, and the backward pass rebuilds masks and yhat from `raw`, never from an activation -- so
 // the skip conv runs conv + finalize and NO apply pass, and the last conv's apply forms both terms here: two raw tensors in, one
-// activation out (the two-pass form writes the skip activation and reads it back).  Each term is formed exactly as
-// bn_train_apply_kernel<0, 0> forms it and added where that kernel adds `res`: the output is bit-identical.  fp32 storage,
+// activation out (the two-pass form writes the skip activation and reads it back).  Each term is bn_affine
+// (bn_math.h), the expression bn_train_apply_kernel stores, added where that kernel adds `res`: the output is bit-identical.  fp32 storage,
 // coefficients from finalize launches (MODE 0), blockIdx.y = micro-batch group; b.res is unused.
 struct BnJoinParams {
     BnTrainParams b;                            // the last conv of the module: raw, scale | shift, relu, out, groups
@@ -551,8 +553,8 @@ __global__ __launch_bounds__(256) void bn_train_join_kernel(const BnJoinParams q
         for (int u = 0; u < kRows; ++u) {
             const long m = m0 + u * stride;
             if (m >= p.M) break;
-            float v[4] = {x[u].x * sc[0] + sh[0], x[u].y * sc[1] + sh[1], x[u].z * sc[2] + sh[2], x[u].w * sc[3] + sh[3]};
-            float w[4] = {y[u].x * sc2[0] + sh2[0], y[u].y * sc2[1] + sh2[1], y[u].z * sc2[2] + sh2[2], y[u].w * sc2[3] + sh2[3]};
+            float v[4] = {bn_affine(x[u].x, sc[0], sh[0]), bn_affine(x[u].y, sc[1], sh[1]), bn_affine(x[u].z, sc[2], sh[2]), bn_affine(x[u].w, sc[3], sh[3])};
+            float w[4] = {bn_affine(y[u].x, sc2[0], sh2[0]), bn_affine(y[u].y, sc2[1], sh2[1]), bn_affine(y[u].z, sc2[2], sh2[2]), bn_affine(y[u].w, sc2[3], sh2[3])};
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 if (p.relu) v[k] = fmaxf(v[k], 0.f);
@@ -600,6 +602,38 @@ struct BnBwdParams {
     int fin_split;                              // finalize launch: waves per group (launch_bn_*_finalize sets it)
 };
 
+// The three dx coefficients of a channel from its forward values and the folded sums sg = sum g, sgy = sum g*yhat over M rows, and
+// what those sums add to dgamma (to dbeta they add (float)sg).  Plain expressions, as bn_math.h's.
+struct BnBwdCoefs { float c1, c2, c3; };
+__device__ __forceinline__ BnBwdCoefs bn_bwd_coefs(float gamma, float r, float istd, double sg, double sgy, double M) {
+    return {gamma * r * istd, (float)(sg / M), (float)(sgy / M)};
+}
+__device__ __forceinline__ float bn_dgamma_term(float r, float d, float fsg, float fsgy) { return r * fsgy + d * fsg; }
+
+// The tail of a pass that reduces backward sums: each thread's a[4] = sum g, b[4] = sum g*yhat of its four channels -> LDS -> the
+// workgroup's fp64 partial row `row` of part[2][C][rows], the row phases added in index order.  All 256 threads call it.
+__device__ __forceinline__ void bn_bwd_partial_row(const double (&a)[4], const double (&b)[4], int c4n, int C, double* part, int rows,
+                                                   int row) {
+    __shared__ double s1[256 * 4];
+    __shared__ double s2[256 * 4];
+    const int tid = threadIdx.x, rpb = 256 / c4n;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { s1[tid * 4 + k] = a[k]; s2[tid * 4 + k] = b[k]; }
+    __syncthreads();
+    if (tid < c4n) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int c = tid * 4 + k;
+            if (c < C) {
+                double ta = 0.0, tb = 0.0;
+                for (int r = 0; r < rpb; ++r) { ta += s1[(r * c4n + tid) * 4 + k]; tb += s2[(r * c4n + tid) * 4 + k]; }
+                part[(long)c * rows + row] = ta;
+                part[((long)C + c) * rows + row] = tb;
+            }
+        }
+    }
+}
+
 template <int R16 = 0>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const BnBwdParams p_in) {
     constexpr int kRows = BnRows<R16>::value;                 // rows (independent loads per tensor) a thread keeps in flight
@@ -614,8 +648,6 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const BnBwdParams p_
         p.M = p.Mg;
         part_row += (int)g * (int)gridDim.x; part_rows *= (int)gridDim.y;
     }
-    __shared__ double s1[256 * 4];
-    __shared__ double s2[256 * 4];
     const int c4n = p.raw_cs / 4;
     const int rpb = 256 / c4n;
     const int tid = threadIdx.x;
@@ -662,29 +694,15 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const BnBwdParams p_
                 }
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    if (p.relu && !(x[k] * sc[k] + sh[k] > 0.f)) g[k] = 0.f;
-                    const float yh = (x[k] - mean[k]) * istd[k];
+                    if (p.relu && !(bn_affine(x[k], sc[k], sh[k]) > 0.f)) g[k] = 0.f;
+                    const float yh = bn_yhat(x[k], mean[k], istd[k]);
                     a[k] += (double)g[k];
                     b[k] += (double)g[k] * (double)yh;
                 }
             }
         }
     }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { s1[tid * 4 + k] = a[k]; s2[tid * 4 + k] = b[k]; }
-    __syncthreads();
-    if (tid < c4n) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int c = tid * 4 + k;
-            if (c < p.C) {
-                double ta = 0.0, tb = 0.0;
-                for (int r = 0; r < rpb; ++r) { ta += s1[(r * c4n + tid) * 4 + k]; tb += s2[(r * c4n + tid) * 4 + k]; }
-                p.part[(long)c * part_rows + part_row] = ta;                       // [2][C][rows]
-                p.part[((long)p.C + c) * part_rows + part_row] = tb;
-            }
-        }
-    }
+    bn_bwd_partial_row(a, b, c4n, p.C, p.part, part_rows, part_row);
 }
 
 // (mapping: bn_fwd_finalize_kernel)  coefficients per group; dbeta / dgamma summed over the groups in order
@@ -708,16 +726,15 @@ __global__ __launch_bounds__(64 * kBnFinalizeWaves) void bn_bwd_finalize_kernel(
     double sg = 0.0, sgy = 0.0;
     if (lane < G) {
         for (int k = 0; k < p.fin_split; ++k) { sg += s_a[lane * p.fin_split + k]; sgy += s_b[lane * p.fin_split + k]; }
+        const BnBwdCoefs k = bn_bwd_coefs(gam, r, istd, sg, sgy, Mg);
         float* coef = p.coef + (long)lane * 3 * p.C;
-        coef[0 * p.C + c] = gam * r * istd;
-        coef[1 * p.C + c] = (float)(sg / Mg);
-        coef[2 * p.C + c] = (float)(sgy / Mg);
+        coef[0 * p.C + c] = k.c1; coef[1 * p.C + c] = k.c2; coef[2 * p.C + c] = k.c3;
     }
     const float fsg = (float)sg, fsgy = (float)sgy;
     for (int g = 0; g < G; ++g) {                             // dbeta / dgamma: the groups' terms added in order
         const float a = __shfl(fsg, g), b = __shfl(fsgy, g), rg = __shfl(r, g), dgp = __shfl(d, g);
         db = db + a;
-        dg = dg + (rg * b + dgp * a);
+        dg = dg + bn_dgamma_term(rg, dgp, a, b);
     }
     if (lane == 0) { p.dbeta[c] = db; p.dgamma[c] = dg; }
 }
@@ -755,12 +772,11 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BnBwdParams p_i
                 double sg, sgy;
                 fold_partials_wave(p.part, p.part_rows, p.C, c, sg, sgy);
                 if ((threadIdx.x & 63) == 0) {
-                    const float r = p.bnc[2 * p.C + c], d = p.bnc[3 * p.C + c], istd = p.bnc[p.C + c];
-                    p.coef[0 * p.C + c] = p.gamma[c] * r * istd;
-                    p.coef[1 * p.C + c] = (float)(sg / (double)p.M);
-                    p.coef[2 * p.C + c] = (float)(sgy / (double)p.M);
+                    const float r = p.bnc[2 * p.C + c], d = p.bnc[3 * p.C + c];
+                    const BnBwdCoefs k = bn_bwd_coefs(p.gamma[c], r, p.bnc[p.C + c], sg, sgy, (double)p.M);
+                    p.coef[0 * p.C + c] = k.c1; p.coef[1 * p.C + c] = k.c2; p.coef[2 * p.C + c] = k.c3;
                     p.dbeta[c] += (float)sg;
-                    p.dgamma[c] += r * (float)sgy + d * (float)sg;
+                    p.dgamma[c] += bn_dgamma_term(r, d, (float)sg, (float)sgy);
                 }
             }
             bn_handoff_publish(p.flag, 1);
@@ -771,23 +787,21 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BnBwdParams p_i
     const int bid = (int)blockIdx.x - nprod, nblk = (int)gridDim.x - nprod;
     if (FUSE) {
         for (int c = threadIdx.x; c < p.raw_cs; c += 256) {
-            float k1 = 0.f, k2 = 0.f, k3 = 0.f;
+            BnBwdCoefs k{};
             if (c < p.C) {
                 double sg = 0.0, sgy = 0.0;
                 for (int r = 0; r < p.part_rows; ++r) {
                     sg += p.part[(long)c * p.part_rows + r];
                     sgy += p.part[((long)p.C + c) * p.part_rows + r];
                 }
-                const float r_ = p.bnc[2 * p.C + c], d_ = p.bnc[3 * p.C + c], istd_ = p.bnc[p.C + c];
-                k1 = p.gamma[c] * r_ * istd_;
-                k2 = (float)(sg / (double)p.M);
-                k3 = (float)(sgy / (double)p.M);
+                const float r_ = p.bnc[2 * p.C + c], d_ = p.bnc[3 * p.C + c];
+                k = bn_bwd_coefs(p.gamma[c], r_, p.bnc[p.C + c], sg, sgy, (double)p.M);
                 if (bid == 0) {
                     p.dbeta[c] += (float)sg;
-                    p.dgamma[c] += r_ * (float)sgy + d_ * (float)sg;
+                    p.dgamma[c] += bn_dgamma_term(r_, d_, (float)sg, (float)sgy);
                 }
             }
-            s_c[0][c] = k1; s_c[1][c] = k2; s_c[2][c] = k3;
+            s_c[0][c] = k.c1; s_c[1][c] = k.c2; s_c[2][c] = k.c3;
         }
         __syncthreads();
     }
@@ -866,9 +880,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BnBwdParams p_i
             float o[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                if (p.relu && !(x[k] * sc[k] + sh[k] > 0.f)) g[k] = 0.f;
-                const float yh = (x[k] - mean[k]) * istd[k];
-                o[k] = (cg * 4 + k < p.C) ? c1[k] * (g[k] - c2[k] - yh * c3[k]) : 0.f;
+                if (p.relu && !(bn_affine(x[k], sc[k], sh[k]) > 0.f)) g[k] = 0.f;
+                const float yh = bn_yhat(x[k], mean[k], istd[k]);
+                o[k] = (cg * 4 + k < p.C) ? bn_dx(c1[k], c2[k], c3[k], g[k], yh) : 0.f;
             }
             if (p.draw_bf16) {
                 const dr_f32x4 f = {o[0], o[1], o[2], o[3]};
@@ -883,8 +897,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BnBwdParams p_i
 // Backward of the joined projection residual (bn_train_join_kernel): the last conv's apply pass.  d(skip activation) = dOut, so
 // instead of copying dOut into a gradient buffer of the skip activation (and the skip conv reading it back in a reduce pass of
 // its own) this pass also loads the skip conv's raw output and reduces ITS backward sums -- sum g2, sum g2 * yhat2 with
-// g2 = dOut * [raw2 * scale2 + shift2 > 0] -- into one fp64 partial row per workgroup, bn_bwd_reduce_kernel's layout and fixed
-// in-block order (rows of group g behind those of group g-1; no floating-point atomics).  The skip conv then runs finalize on
+// g2 = dOut * [bn_affine(raw2, scale2, shift2) > 0] -- into one fp64 partial row per workgroup through bn_bwd_partial_row, the tail
+// bn_bwd_reduce_kernel ends on (rows of group g behind those of group g-1; no floating-point atomics).  The skip conv then runs finalize on
 // those rows and an apply pass that reads dOut from this layer's output gradient.  fp32 storage, MODE 0 coefficients,
 // blockIdx.y = micro-batch group; b.dres is unused.
 struct BnBwdJoinParams {
@@ -912,8 +926,6 @@ __global__ __launch_bounds__(256) void bn_bwd_join_kernel(const BnBwdJoinParams 
         p.M = p.Mg;
         part_row += (int)g * (int)gridDim.x; part_rows *= (int)gridDim.y;
     }
-    __shared__ double s1[256 * 4];
-    __shared__ double s2[256 * 4];
     const int c4n = p.raw_cs / 4;
     const int rpb = 256 / c4n;
     const int tid = threadIdx.x;
@@ -968,33 +980,19 @@ __global__ __launch_bounds__(256) void bn_bwd_join_kernel(const BnBwdJoinParams 
                 float o[4];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const float g2 = (y[k] * sc2[k] + sh2[k] > 0.f) ? g[k] : 0.f;       // the skip branch: always ReLU
-                    const float yh2 = (y[k] - mean2[k]) * istd2[k];
+                    const float g2 = (bn_affine(y[k], sc2[k], sh2[k]) > 0.f) ? g[k] : 0.f;       // the skip branch: always ReLU
+                    const float yh2 = bn_yhat(y[k], mean2[k], istd2[k]);
                     a[k] += (double)g2;
                     b[k] += (double)g2 * (double)yh2;
-                    if (p.relu && !(x[k] * sc[k] + sh[k] > 0.f)) g[k] = 0.f;
-                    const float yh = (x[k] - mean[k]) * istd[k];
-                    o[k] = (cg * 4 + k < p.C) ? c1[k] * (g[k] - c2[k] - yh * c3[k]) : 0.f;
+                    if (p.relu && !(bn_affine(x[k], sc[k], sh[k]) > 0.f)) g[k] = 0.f;
+                    const float yh = bn_yhat(x[k], mean[k], istd[k]);
+                    o[k] = (cg * 4 + k < p.C) ? bn_dx(c1[k], c2[k], c3[k], g[k], yh) : 0.f;
                 }
                 bn_st4(p.draw + m * p.raw_cs + cg * 4, make_float4(o[0], o[1], o[2], o[3]));
             }
         }
     }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { s1[tid * 4 + k] = a[k]; s2[tid * 4 + k] = b[k]; }
-    __syncthreads();
-    if (tid < c4n) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int c = tid * 4 + k;
-            if (c < p.C) {
-                double ta = 0.0, tb = 0.0;
-                for (int r = 0; r < rpb; ++r) { ta += s1[(r * c4n + tid) * 4 + k]; tb += s2[(r * c4n + tid) * 4 + k]; }
-                q.part2[(long)c * part_rows + part_row] = ta;                      // [2][C][rows]
-                q.part2[((long)p.C + c) * part_rows + part_row] = tb;
-            }
-        }
-    }
+    bn_bwd_partial_row(a, b, c4n, p.C, q.part2, part_rows, part_row);
 }
 
 // bias convs: g(m,c) = dOut(m,c) * factor * [out(m,c) > 0 if relu]  -> dense scratch (stride gcs), pads zero
@@ -1127,12 +1125,13 @@ __global__ __launch_bounds__(256) void upsample_add_bwd_kernel(View dout, View d
 
 // ------------------------------------------------------------------------------------------------
 // Loss: target synthesis + l2 losses + gradient seeds for every stack, one thread per map pixel.
-// fp32 in the reference's op order (contraction off), see oracle/pose.py make_targets.
+// The targets are pose_math.h's (map_cam, cloud_point, pose_targets), the definition loss_report.h shares.
 // ------------------------------------------------------------------------------------------------
 constexpr int kMaxStack = 8;
+struct StackMaps { View hm[kMaxStack], hm3[kMaxStack], um[kMaxStack]; };   // one view per stack and head (densereg.cpp stack_maps)
 struct LossParams {
-    View hm[kMaxStack], hm3[kMaxStack], um[kMaxStack];        // predictions
-    View dhm[kMaxStack], dhm3[kMaxStack], dum[kMaxStack];     // gradient seeds (written)
+    StackMaps pred;                                           // predictions
+    StackMaps seed;                                           // gradient seeds (written)
     int S, B, h, w, J;
     const float* tiny; const float* pose; const float* cfg; const float* com;
     double* acc;                                              // [3] hm, hm3, um (sum x^2 / 2)
@@ -1153,44 +1152,18 @@ __global__ __launch_bounds__(256) void loss_kernel(const LossParams p) {
         const int j = (int)(idx % p.J);
         const int i = (int)(idx / p.J);
         const int b = i / npix, px = i % npix;
-        const float* cfg = p.cfg + b * 6;
-        const float cx0 = p.com[b * 3 + 0], cy0 = p.com[b * 3 + 1], cz0 = p.com[b * 3 + 2];
-        const float w_ratio = cfg[4] / (float)p.w, h_ratio = cfg[5] / (float)p.h;
-        const float fx = cfg[0] / w_ratio, fy = cfg[1] / h_ratio, cx = cfg[2] / w_ratio, cy = cfg[3] / h_ratio;
-        const float xx = (float)(px % p.w), yy = (float)(px / p.w);
-        // point cloud at this pixel (preprocess.py:202-225)
-        const float t = p.tiny[i];
-        const float min_depth = cz0 - 300.0f * 0.5f, max_depth = cz0 + 300.0f * 0.5f;
-        const float zz = (t < -0.99f) ? max_depth : (t * 300.0f + min_depth);
-        float X = (xx - cx) * (zz / fx);
-        float Y = (yy - cy) * (zz / fy);
-        X = (X - cx0) / 100.0f;
-        Y = (Y - cy0) / 100.0f;
-        const float Z = (zz - cz0) / 100.0f;
-        const float* ps = p.pose + (long)b * 3 * p.J + 3 * j;
-        // 2D cone (:225-242)
-        const float u = ps[0] * fx / ps[2] + cx;
-        const float v = ps[1] * fy / ps[2] + cy;
-        const float du = xx - u, dv = yy - v;
-        const float gt_hm = fmaxf(4.0f - sqrtf(du * du + dv * dv), 0.0f) / 4.0f;
-        // 3D offsets (:338-346)
-        const float ox = (ps[0] - cx0) / 100.0f - X;
-        const float oy = (ps[1] - cy0) / 100.0f - Y;
-        const float oz = (ps[2] - cz0) / 100.0f - Z;
-        const float dist = sqrtf((ox * ox + oy * oy) + oz * oz);
-        const float gt_hm3 = fmaxf((0.8f - dist) / 0.8f, 0.0f);
-        const float d3 = 0.8f - gt_hm3 * 0.8f;
-        const bool near = d3 < (0.8f - 1e-2f);
-        const float ux = near ? ox / d3 : 0.0f, uy = near ? oy / d3 : 0.0f, uz = near ? oz / d3 : 0.0f;
+        const MapCam cam = map_cam(p.cfg + b * 6, p.w, p.h);
+        const CloudPoint cloud = cloud_point(cam, p.com + b * 3, p.tiny[i], px, p.w);
+        const PoseTargets gt = pose_targets(cam, p.com + b * 3, p.pose + (long)b * 3 * p.J + 3 * j, cloud, px, p.w);
         for (int s = 0; s < p.S; ++s) {
             const long m = i;
-            const float e1 = p.hm[s].p[m * p.hm[s].cs + p.hm[s].coff + j] - gt_hm;
-            const float e2 = p.hm3[s].p[m * p.hm3[s].cs + p.hm3[s].coff + j] - gt_hm3;
-            const float* um = p.um[s].p + m * p.um[s].cs + p.um[s].coff + 3 * j;
-            const float e3 = um[0] - ux, e4 = um[1] - uy, e5 = um[2] - uz;
-            p.dhm[s].p[m * p.dhm[s].cs + p.dhm[s].coff + j] = e1;
-            p.dhm3[s].p[m * p.dhm3[s].cs + p.dhm3[s].coff + j] = e2;
-            float* dum = p.dum[s].p + m * p.dum[s].cs + p.dum[s].coff + 3 * j;
+            const float e1 = p.pred.hm[s].p[m * p.pred.hm[s].cs + p.pred.hm[s].coff + j] - gt.gt_hm;
+            const float e2 = p.pred.hm3[s].p[m * p.pred.hm3[s].cs + p.pred.hm3[s].coff + j] - gt.gt_hm3;
+            const float* um = p.pred.um[s].p + m * p.pred.um[s].cs + p.pred.um[s].coff + 3 * j;
+            const float e3 = um[0] - gt.ux, e4 = um[1] - gt.uy, e5 = um[2] - gt.uz;
+            p.seed.hm[s].p[m * p.seed.hm[s].cs + p.seed.hm[s].coff + j] = e1;
+            p.seed.hm3[s].p[m * p.seed.hm3[s].cs + p.seed.hm3[s].coff + j] = e2;
+            float* dum = p.seed.um[s].p + m * p.seed.um[s].cs + p.seed.um[s].coff + 3 * j;
             dum[0] = e3; dum[1] = e4; dum[2] = e5;
             l_hm += 0.5 * (double)e1 * e1;
             l_hm3 += 0.5 * (double)e2 * e2;
@@ -1271,18 +1244,27 @@ __global__ __launch_bounds__(256) void grad_merge_kernel(float* a, float* b, lon
 
 // Fused accumulate-average / clip / Adam over the flat buffers (train_single_gpu.py:86-89).
 //   g = clip(acc/div, +-clip) ; m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ; theta -= lr_t m/(sqrt(v)+eps)
+// adam_elem is the one definition of an element's step: adam_kernel applies it, step_report.h describes it.
 // ------------------------------------------------------------------------------------------------
+struct AdamElem { float a, g, m, v, u; };      // averaged gradient, clipped gradient, new moments, decrement of the weight
+__device__ __forceinline__ AdamElem adam_elem(float acc, float m0, float v0, float div, float clip, float lr_t, float b1, float b2,
+                                              float eps) {
+#pragma clang fp contract(off)
+    const float a = acc / div;
+    const float g = fminf(fmaxf(a, -clip), clip);
+    const float mi = b1 * m0 + (1.0f - b1) * g;
+    const float vi = b2 * v0 + (1.0f - b2) * g * g;
+    return {a, g, mi, vi, lr_t * mi / (sqrtf(vi) + eps)};
+}
+
 __global__ __launch_bounds__(256) void adam_kernel(float* param, const float* grad, float* m, float* v, long n, float div,
                                                    float clip, float lr_t, float b1, float b2, float eps) {
 #pragma clang fp contract(off)
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        float g = grad[i] / div;
-        g = fminf(fmaxf(g, -clip), clip);
-        const float mi = b1 * m[i] + (1.0f - b1) * g;
-        const float vi = b2 * v[i] + (1.0f - b2) * g * g;
-        m[i] = mi;
-        v[i] = vi;
-        param[i] = param[i] - lr_t * mi / (sqrtf(vi) + eps);
+        const AdamElem e = adam_elem(grad[i], m[i], v[i], div, clip, lr_t, b1, b2, eps);
+        m[i] = e.m;
+        v[i] = e.v;
+        param[i] = param[i] - e.u;
     }
 }
 

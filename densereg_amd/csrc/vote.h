@@ -22,9 +22,11 @@
 // vote_report_kernel is the same body (vote_body<true>) that also stores what the reference's test graph exposes as its "interface to
 // fetch output" (:464-471, 521-526, 781-784) -- uvd joints, candidates, their point-cloud positions, weights, the heat-map-only peak --
 // and the kernel mass at the final centre, each behind a nullable pointer (struct VoteReport).  Same geometry, LDS plan and xyz bits.
+// The crop camera and the point cloud at a candidate pixel are pose_math.h's map_cam and cloud_point, the functions the loss targets use.
 #pragma once
 #include "dr_platform.h"
 #include "kernels_misc.h"
+#include "pose_math.h"
 
 namespace dr {
 
@@ -108,7 +110,7 @@ __device__ __forceinline__ void vote_body(const VoteParams& p, const VoteReport&
     // ---- phase 1: refined heat-map of joints j0..j0+3 into LDS ---------------------------------
     for (int px = tid; px < npix; px += 256) {
         const long m = (long)b * npix + px;
-        const float fg = (p.tiny[m] < -0.99f) ? 0.0f : 1.0f;
+        const float fg = (p.tiny[m] < kBackground) ? 0.0f : 1.0f;
         const float* hm = p.hm.p + m * p.hm.cs + p.hm.coff;
         const float* h3 = p.hm3.p + m * p.hm3.cs + p.hm3.coff;
 #pragma unroll
@@ -175,10 +177,7 @@ __device__ __forceinline__ void vote_body(const VoteParams& p, const VoteReport&
     // ---- candidates + weights: lane i < 5 owns candidate i ------------------------------------
     const float* cfg = p.cfg + b * 6;
     const float cx0 = p.com[b * 3 + 0], cy0 = p.com[b * 3 + 1], cz0 = p.com[b * 3 + 2];
-    const float w_ratio = cfg[4] / (float)p.w;
-    const float h_ratio = cfg[5] / (float)p.h;
-    const float fx = cfg[0] / w_ratio, fy = cfg[1] / h_ratio;
-    const float cx = cfg[2] / w_ratio, cy = cfg[3] / h_ratio;
+    const MapCam cam = map_cam(cfg, p.w, p.h);
     float c0 = 0.f, c1 = 0.f, c2 = 0.f, wt = 0.f;
     {
         const int me = lane < 5 ? lane : 0;
@@ -186,27 +185,18 @@ __device__ __forceinline__ void vote_body(const VoteParams& p, const VoteReport&
 #pragma unroll
         for (int k = 1; k < 5; ++k) px = (me == k) ? sel[k] : px;
         const long m = (long)b * npix + px;
-        const float t = p.tiny[m];
-        const float min_depth = cz0 - 300.0f * 0.5f;
-        const float max_depth = cz0 + 300.0f * 0.5f;
-        const float zz = (t < -0.99f) ? max_depth : (t * 300.0f + min_depth);
-        const float xx = (float)(px % p.w), yy = (float)(px / p.w);
-        float X = (xx - cx) * (zz / fx);
-        float Y = (yy - cy) * (zz / fy);
-        X = (X - cx0) / 100.0f;
-        Y = (Y - cy0) / 100.0f;
-        const float Z = (zz - cz0) / 100.0f;
+        const CloudPoint cloud = cloud_point(cam, p.com + b * 3, p.tiny[m], px, p.w);
         // resume_om: um * (0.8 - hm3*0.8)
         const float h3 = p.hm3.p[m * p.hm3.cs + p.hm3.coff + j];
-        const float d3 = 0.8f - h3 * 0.8f;
+        const float d3 = kOffsetRadius - h3 * kOffsetRadius;
         const float* um = p.um.p + m * p.um.cs + p.um.coff + 3 * j;
-        c0 = X + um[0] * d3;
-        c1 = Y + um[1] * d3;
-        c2 = Z + um[2] * d3;
+        c0 = cloud.X + um[0] * d3;
+        c1 = cloud.Y + um[1] * d3;
+        c2 = cloud.Z + um[2] * d3;
         // weight = hm at the re-projected pixel (raw hm; out of range -> 0)
-        const float ux = c0 * 100.0f + cx0, uy = c1 * 100.0f + cy0, uz = c2 * 100.0f + cz0;
-        const float uf = (ux * fx / uz + cx) + 0.5f;
-        const float vf = (uy * fy / uz + cy) + 0.5f;
+        const float ux = c0 * kPoseScale + cx0, uy = c1 * kPoseScale + cy0, uz = c2 * kPoseScale + cz0;
+        const float uf = (ux * cam.fx / uz + cam.cx) + 0.5f;
+        const float vf = (uy * cam.fy / uz + cam.cy) + 0.5f;
         wt = 0.f;
         if (uf > -1.0f && uf < (float)p.w && vf > -1.0f && vf < (float)p.h) {      // NaN fails
             const int uu = (int)uf, vv = (int)vf;                                      // trunc toward 0
@@ -220,7 +210,7 @@ __device__ __forceinline__ void vote_body(const VoteParams& p, const VoteReport&
                 if (rep.can_score) rep.can_score[o] = rj[px];
                 if (rep.can_weight) rep.can_weight[o] = wt;
                 if (rep.can_pts) { rep.can_pts[3 * o + 0] = c0; rep.can_pts[3 * o + 1] = c1; rep.can_pts[3 * o + 2] = c2; }
-                if (rep.ori_pts) { rep.ori_pts[3 * o + 0] = X; rep.ori_pts[3 * o + 1] = Y; rep.ori_pts[3 * o + 2] = Z; }
+                if (rep.ori_pts) { rep.ori_pts[3 * o + 0] = cloud.X; rep.ori_pts[3 * o + 1] = cloud.Y; rep.ori_pts[3 * o + 2] = cloud.Z; }
             }
         }
     }
@@ -285,7 +275,7 @@ __device__ __forceinline__ void vote_body(const VoteParams& p, const VoteReport&
         const float cm = lane == 0 ? cx0 : (lane == 1 ? cy0 : cz0);
         const long o = (long)b * 3 * J + 3 * j + lane;
         if (p.xyz_norm) p.xyz_norm[o] = cn;
-        p.xyz_mm[o] = cn * 100.0f + cm;
+        p.xyz_mm[o] = cn * kPoseScale + cm;
     }
     if constexpr (REPORT) {
         // kernel mass at the final centre, once after the loop (or its early break): the reference's own kernel weight
@@ -301,7 +291,7 @@ __device__ __forceinline__ void vote_body(const VoteParams& p, const VoteReport&
         }
         // xyz2uvd_op with the crop's own camera, unscaled (data/util.py:20 _pro): u = (x*fx)/z + cx, v = (y*fy)/z + cy, d = z
         if (rep.uvd && lane < 3) {
-            const float x = ctr[0] * 100.0f + cx0, y = ctr[1] * 100.0f + cy0, z = ctr[2] * 100.0f + cz0;
+            const float x = ctr[0] * kPoseScale + cx0, y = ctr[1] * kPoseScale + cy0, z = ctr[2] * kPoseScale + cz0;
             const float u = (x * cfg[0]) / z + cfg[2];
             const float v = (y * cfg[1]) / z + cfg[3];
             rep.uvd[((long)b * J + j) * 3 + lane] = lane == 0 ? u : (lane == 1 ? v : z);

@@ -253,7 +253,7 @@ int dr_loss_report(dr_handle* h, int B, const float* dm_norm_dev, const float* p
 /* Per trainable variable, what the reference histograms (train_single_gpu.py:91-95: every variable and every averaged, clipped
  * gradient) and what shows a diverging or dead layer before the step is taken.  V = the number of trainable variables in flat
  * order (dr_param_info with trainable != 0: the layout of dr_flat_param / dr_flat_grad); E = num_edges.  Per element i, with
- * dr_apply_adam's arithmetic restated op for op:  acc = flat_grad[i] (+ the second micro-step set's accumulator where
+ * the per-element function dr_apply_adam itself applies:  acc = flat_grad[i] (+ the second micro-step set's accumulator where
  * dr_sync_grads would add it);  a = acc / div;  g = clip(a, -clip, clip) (a NaN a gives -clip, as in the step);
  * m' = b1 m + (1-b1) g;  v' = b2 v + (1-b2) g g;  u = lr_t m' / (sqrt(v') + eps): the decrement of theta.
  * Device pointers, any output member NULL = not wanted; dense, row-major.  min / max ignore NaN (an all-NaN variable gives NaN),
