@@ -158,17 +158,10 @@ extern "C" int dr_dbg_bn_layer(dr_dbg_bn_args* a, dr_stream stream) {
     if (a->res) fp.res = View{const_cast<float*>(a->res), cs, 0, C};
     fp.out = View{a->y, cs, 0, C};
     fp.out_bf16 = (g_dbg_bf16_storage && !a->res) ? 1 : 0;
-    const int rpb = 256 / (cs / 4);
     if (!rc) {
-        if (fp.part_rows <= kBnFuseRows) {
-            DR_LAUNCH(bn_train_apply_kernel<1>, dim3(grid_for(M, rpb, bn_grid_cap())), dim3(256), 0, s, fp);
-        } else if (lookback) {
-            fp.flag = flags; fp.flag_target = dr_ceil_div(C, 4);
-            DR_LAUNCH(bn_train_apply_kernel<2>, dim3(grid_for(M, rpb, bn_grid_cap()) + dr_ceil_div(C, 4)), dim3(256), 0, s, fp);
-        } else {
-            launch_bn_fwd_finalize(fp, s);
-            DR_LAUNCH(bn_train_apply_kernel<0>, dim3(grid_for(M, rpb, bn_grid_cap())), dim3(256), 0, s, fp);
-        }
+        const BnForm form = bn_form(fp.part_rows, 1, false, lookback);
+        if (form == kBnLookback) { fp.flag = flags; fp.flag_target = dr_ceil_div(C, 4); }
+        rc = launch_bn_fwd_apply(fp, form, s);
     }
     // ---- backward: backward_conv (BatchReNorm part) ------------------------------------------------
     BnBwdParams bp{};
@@ -180,8 +173,8 @@ extern "C" int dr_dbg_bn_layer(dr_dbg_bn_args* a, dr_stream stream) {
     if (!rc && !consumer) {
         rt::d2d(a->dout_used, a->dout, (size_t)M * cs * 4, s);
         bp.dout = View{a->dout_used, cs, 0, C};
-        bp.part = part; bp.part_rows = grid_for(M, rpb * 8, 256);
-        DR_LAUNCH(bn_bwd_reduce_kernel<0>, dim3(bp.part_rows), dim3(256), 0, s, bp);
+        bp.part = part;
+        launch_bn_bwd_reduce(bp, s);
     } else if (!rc) {
         const int tr = a->kr * a->kr;
         DR_LAUNCH(pack_weights_T_kernel, dim3(grid_for((long)tr * KpT * NpT)), dim3(256), 0, s, a->wr, wpT, tr, C, a->Cr, KpT, NpT);
@@ -200,15 +193,9 @@ extern "C" int dr_dbg_bn_layer(dr_dbg_bn_args* a, dr_stream stream) {
     }
     a->bwd_rows = bp.part_rows;
     if (!rc) {
-        if (bp.part_rows <= kBnFuseRows) {
-            DR_LAUNCH(bn_bwd_apply_kernel<1>, dim3(grid_for(M, rpb, bn_grid_cap())), dim3(256), 0, s, bp);
-        } else if (lookback) {
-            bp.flag = flags + 2; bp.flag_target = dr_ceil_div(C, 4);
-            DR_LAUNCH(bn_bwd_apply_kernel<2>, dim3(grid_for(M, rpb, bn_grid_cap()) + dr_ceil_div(C, 4)), dim3(256), 0, s, bp);
-        } else {
-            launch_bn_bwd_finalize(bp, s);
-            DR_LAUNCH(bn_bwd_apply_kernel<0>, dim3(grid_for(M, rpb, bn_grid_cap())), dim3(256), 0, s, bp);
-        }
+        const BnForm form = bn_form(bp.part_rows, 1, false, lookback);
+        if (form == kBnLookback) { bp.flag = flags + 2; bp.flag_target = dr_ceil_div(C, 4); }
+        rc = launch_bn_bwd_apply(bp, form, s);
     }
     rt::sync_stream(s);
     int hflags[4] = {0, 0, 0, 0};
@@ -259,8 +246,6 @@ extern "C" int dr_dbg_bn_join(dr_dbg_bn_join_args* a, dr_stream stream) {
     for (float* q : {a->dgamma_s, a->dbeta_s, a->dgamma_3, a->dbeta_3}) rt::memset_async(q, 0, (size_t)C * 4, s);
     DR_LAUNCH(pack_weights_kernel, dim3(grid_for((long)Kp_s * Np)), dim3(256), 0, s, a->w_s, wp_s, 1, a->Cin_s, C, Kp_s, Np);
     DR_LAUNCH(pack_weights_kernel, dim3(grid_for((long)Kp_3 * Np)), dim3(256), 0, s, a->w_3, wp_3, 1, a->Cin_3, C, Kp_3, Np);
-    const int rpb = 256 / (cs / 4);
-    const dim3 apply_grid = G > 1 ? dim3(grid_for(Mg, rpb, std::max(bn_grid_cap() / G, 64)), G) : dim3(grid_for(M, rpb, bn_grid_cap()));
     int rc = 0;
     // ---- forward: run_conv_train, the skip conv first --------------------------------------------------
     BnTrainParams fp[2];
@@ -280,7 +265,7 @@ extern "C" int dr_dbg_bn_join(dr_dbg_bn_join_args* a, dr_stream stream) {
         rc = launch_conv_igemm(p, s);
         if (rc) break;
         if (own_moments) {
-            const int rows_g = grid_for(std::max<long>(Mg / 8, 1), 1, 1024 / G);
+            const int rows_g = bn_moments_rows(Mg, G);
             part_rows = rows_g * G;
             DR_LAUNCH(moments_kernel, dim3(rows_g, G), dim3(256), 0, s, (const float*)raw, cs, 0, Mg, C, part);
         }
@@ -303,16 +288,11 @@ extern "C" int dr_dbg_bn_join(dr_dbg_bn_join_args* a, dr_stream stream) {
             if (last) {
                 BnJoinParams jp{};
                 jp.b = bp; jp.raw2 = a->raw_s; jp.scale2 = fp[0].scale; jp.shift2 = fp[0].shift;
-                DR_LAUNCH(bn_train_join_kernel, apply_grid, dim3(256), 0, s, jp);
+                launch_bn_fwd_join(jp, s);
             }
         } else {
             if (last) bp.res = View{skip, cs, 0, C};
-            if (G > 1 || bp.part_rows > kBnFuseRows) {
-                launch_bn_fwd_finalize(bp, s);
-                DR_LAUNCH((bn_train_apply_kernel<0, 0>), apply_grid, dim3(256), 0, s, bp);
-            } else {
-                DR_LAUNCH((bn_train_apply_kernel<1, 0>), apply_grid, dim3(256), 0, s, bp);
-            }
+            rc = launch_bn_fwd_apply(bp, bn_form(part_rows, G, false, false), s);
         }
     }
     // ---- backward: backward_conv (BatchReNorm part), the last conv first ----------------------------
@@ -331,27 +311,17 @@ extern "C" int dr_dbg_bn_join(dr_dbg_bn_join_args* a, dr_stream stream) {
         if (joined && !last) {
             bp.part_rows = join_rows;
         } else {
-            const int rows_g = grid_for(Mg, rpb * 8, std::max(256 / G, 32));
-            bp.part_rows = rows_g * G;
-            DR_LAUNCH(bn_bwd_reduce_kernel<0>, dim3(rows_g, G), dim3(256), 0, s, bp);
+            launch_bn_bwd_reduce(bp, s);
         }
         bp.rows_per_group = bp.part_rows / G;
-        if (joined) {
+        if (joined && last) {
             launch_bn_bwd_finalize(bp, s);
-            if (!last) {
-                DR_LAUNCH((bn_bwd_apply_kernel<0, 0>), apply_grid, dim3(256), 0, s, bp);
-            } else {
-                join_rows = (int)(apply_grid.x * apply_grid.y);
-                if ((size_t)join_rows * 2 * C > n_part) { rc = -1; break; }
-                BnBwdJoinParams jp{};
-                jp.b = bp; jp.raw2 = fp[0].raw; jp.scale2 = fp[0].scale; jp.shift2 = fp[0].shift; jp.bnc2 = fp[0].bnc; jp.part2 = part;
-                DR_LAUNCH(bn_bwd_join_kernel, apply_grid, dim3(256), 0, s, jp);
-            }
-        } else if (G > 1 || bp.part_rows > kBnFuseRows) {
-            launch_bn_bwd_finalize(bp, s);
-            DR_LAUNCH((bn_bwd_apply_kernel<0, 0>), apply_grid, dim3(256), 0, s, bp);
+            BnBwdJoinParams jp{};
+            jp.b = bp; jp.raw2 = fp[0].raw; jp.scale2 = fp[0].scale; jp.shift2 = fp[0].shift; jp.bnc2 = fp[0].bnc; jp.part2 = part;
+            join_rows = launch_bn_bwd_join(jp, n_part, s);
+            if (join_rows <= 0) rc = -1;
         } else {
-            DR_LAUNCH((bn_bwd_apply_kernel<1, 0>), apply_grid, dim3(256), 0, s, bp);
+            rc = launch_bn_bwd_apply(bp, bn_form(bp.part_rows, G, joined, false), s);
         }
     }
     a->part_rows = join_rows;
@@ -494,20 +464,17 @@ extern "C" int dr_dbg_bn_bench(long M, int C, int reduce_blocks, int iters, floa
     bp.dout = View{dout, cs, 0, C}; bp.raw = raw; bp.raw_cs = cs; bp.M = M; bp.C = C; bp.relu = 1;
     bp.scale = small + 6144; bp.shift = small + 7168; bp.bnc = small + 8192; bp.gamma = small + 1024;
     bp.dbeta = small + 12288; bp.dgamma = small + 13312; bp.draw = draw; bp.coef = small + 9216;
-    const int rpb = 256 / (cs / 4);
-    const int g_apply = grid_for(M, rpb, bn_grid_cap());
-    const int g_reduce = reduce_blocks > 0 ? reduce_blocks : grid_for(M, rpb * 8, 256);
-    bp.part = bpart; bp.part_rows = g_reduce;
+    bp.part = bpart;
+    // the finalize-launch form whatever the partial rows (one here; the rule would fold it in the apply pass): the large layers' passes
     auto time_it = [&](int which) {
         auto launch = [&]() {
             if (which == 0) {
-                launch_bn_fwd_finalize(fp, (hipStream_t) nullptr);
-                DR_LAUNCH(bn_train_apply_kernel<0>, dim3(g_apply), dim3(256), 0, (hipStream_t) nullptr, fp);
+                launch_bn_fwd_apply(fp, kBnFinalize, (hipStream_t) nullptr);
             } else if (which == 1) {
-                DR_LAUNCH(bn_bwd_reduce_kernel<0>, dim3(g_reduce), dim3(256), 0, (hipStream_t) nullptr, bp);
+                launch_bn_bwd_reduce(bp, (hipStream_t) nullptr, reduce_blocks);
                 launch_bn_bwd_finalize(bp, (hipStream_t) nullptr);
             } else {
-                DR_LAUNCH(bn_bwd_apply_kernel<0>, dim3(g_apply), dim3(256), 0, (hipStream_t) nullptr, bp);
+                launch_bn_bwd_apply(bp, kBnFinalize, (hipStream_t) nullptr, false);       // (its finalize is timed with the reduce)
             }
         };
         for (int i = 0; i < 3; ++i) launch();

@@ -46,13 +46,6 @@ static std::string g_create_err;
 // (PyTorch) may have moved it
 #define DR_ENTER(h) (void)rt::set_device((h)->cfg.device)
 
-static inline int grid_for(long total, int block = 256, int cap = 0) {
-    static const int dflt = [] { const char* e = getenv("DR_ELT_GRID"); const int v = e ? atoi(e) : 0; return v >= 64 ? v : 256 * 8; }();
-    if (cap <= 0) cap = dflt;                                  // grid-stride elementwise kernels (experiment switch DR_ELT_GRID)
-    long g = (total + block - 1) / block;
-    return (int)std::max<long>(1, std::min<long>(g, cap));
-}
-
 // ==============================================================================================
 // conv launcher
 // ==============================================================================================
@@ -1803,8 +1796,7 @@ int dr_read_activation(dr_handle* h, const char* scope, int B, float* host, size
             bp.scale = h->fold + c.fold_off; bp.shift = h->fold + c.fold_off + c.cout;
             bp.res = View{nullptr, 0, 0, 0}; bp.out = op.out.fwd();
             bp.groups = G; bp.Mg = M / G; bp.fold_stride = (long)h->n_fold; bp.bnc_stride = (long)h->n_bnc;
-            const int rpb = 256 / (c.raw->cs / 4);
-            DR_LAUNCH((bn_train_apply_kernel<0, 0>), dim3(grid_for(bp.Mg, rpb, 512), G), dim3(256), 0, (hipStream_t) nullptr, bp);
+            launch_bn_fwd_apply(bp, kBnFinalize, (hipStream_t) nullptr, false);      // (the forward's finalize launch left the coefficients)
         }
         if (t->is_bf16)                     // stored as bf16 by the training forward of the bf16 path (its only reader is a conv): widen
             DR_LAUNCH(copy_channels_from_bf16_kernel, dim3(grid_for(M * op.out.C)), dim3(256), 0, (hipStream_t) nullptr,

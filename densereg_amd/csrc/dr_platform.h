@@ -2,6 +2,7 @@
 // or for the host-fiber emulator used by the CPU-side unit tests (tests/hipemu, -DDR_EMU).
 #pragma once
 
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <cstdio>
@@ -273,3 +274,9 @@ typedef float dr_f32x4 __attribute__((ext_vector_type(4)));
 
 __host__ __device__ static inline int dr_ceil_div(int a, int b) { return (a + b - 1) / b; }
 __host__ __device__ static inline int dr_round_up(int a, int b) { return dr_ceil_div(a, b) * b; }
+static inline int grid_for(long total, int block = 256, int cap = 0) {
+    static const int dflt = [] { const char* e = getenv("DR_ELT_GRID"); const int v = e ? atoi(e) : 0; return v >= 64 ? v : 256 * 8; }();
+    if (cap <= 0) cap = dflt;                                  // grid-stride elementwise kernels (experiment switch DR_ELT_GRID)
+    long g = (total + block - 1) / block;
+    return (int)std::max<long>(1, std::min<long>(g, cap));
+}

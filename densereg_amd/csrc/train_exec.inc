@@ -15,9 +15,6 @@ void launch_wgrad_square(const WgradParams& p, int T, dim3 grid, hipStream_t s);
 bool wgrad_use_x3();
 void plan_backward(dr_handle* h);
 
-// BatchReNorm layers with at most this many partial rows fold them inside the apply kernels (train_kernels.h).
-// (80, which would cover the 8x8-pixel layers on the split-K kernel's 32-row tiles, measured slower: 1767 vs 1782 crops/s.)
-constexpr int kBnFuseRows = 48;
 // workgroups per regularised variable in reg_loss_kernel (8 left the 590k-element weights as a 288-deep chain of
 // dependent loads: 118 us)
 constexpr int kRegRows = 64;
@@ -248,13 +245,6 @@ int alloc_training_state(dr_handle* h) {
 }
 
 inline long rows_of(const Tensor* t, int B) { return (long)B * t->H * t->W; }
-// Workgroup cap of the BatchReNorm streaming passes: 512 = two per CU, each thread keeping kBnRows 16-byte loads per tensor in
-// flight.  Measured on the training step (DR_BN_GRID overrides): 8192 -> 1808 crops/s, 4096 -> 1874, 2048 (round 1) -> 1931,
-// 1024 -> 1964, 768 -> 1967, 512 -> 1969-1974, 384 -> 1954, 256 -> 1957; eight rows in flight instead of four: no difference.
-inline int bn_grid_cap() {
-    static const int cap = [] { const char* e = getenv("DR_BN_GRID"); const int v = e ? atoi(e) : 0; return v >= 64 ? v : 512; }();
-    return cap;
-}
 
 // Decide, once per graph, who writes each gradient buffer first in the reverse sweep.  A first writer that
 // covers the whole tensor overwrites (no zero fill, no read-modify-write); only buffers whose first writer is
@@ -460,7 +450,7 @@ int run_conv_train(dr_handle* h, const Op& op, int B, hipStream_t s) {
             DR_LAUNCH(stem_conv_kernel, dim3(dr_ceil_div((int)M, 64)), dim3(256), 0, s, sp);
         }
         ProfScope ps(h, s, KID_BN, 0.0, 4.0 * M * c.cout);
-        const int rows_g = grid_for(Mg / 8, 1, 1024 / G);   // one partial row per workgroup, folded like a conv epilogue's rows
+        const int rows_g = bn_moments_rows(Mg, G);          // one partial row per workgroup, folded like a conv epilogue's rows
         part_rows = rows_g * G;
         double* rows = h->stat_part_l[op.lane];
         part = rows;
@@ -529,7 +519,7 @@ int run_conv_train(dr_handle* h, const Op& op, int B, hipStream_t s) {
         bp.out_bf16 = a16 ? 1 : 0;
     }
     if (raw->cs / 4 > 256) DR_FAIL(h, DR_E_UNSUPPORTED, "BatchReNorm layer wider than 1024 channels");
-    const int rpb = 256 / (raw->cs / 4);
+    const BnForm form = bn_form(bp.part_rows, G, op.join_role != 0, h->bn_lookback);
     if (op.join_role) {                                      // joined projection residual: always the finalize-launch form
         if (raw->is_bf16 || bp.out_bf16 || h->precision != 0 || h->bn_lookback) DR_FAIL(h, DR_E_STATE, "conv %s: joined BatchReNorm branches need the fp32 path", c.name.c_str());
         launch_bn_fwd_finalize(bp, s);
@@ -539,26 +529,14 @@ int run_conv_train(dr_handle* h, const Op& op, int B, hipStream_t s) {
         BnJoinParams jp{};
         jp.b = bp; jp.b.res = View{nullptr, 0, 0, 0};
         jp.raw2 = cs.raw->p; jp.scale2 = h->fold + cs.fold_off; jp.shift2 = h->fold + cs.fold_off + cs.cout;
-        if (G > 1) DR_LAUNCH(bn_train_join_kernel, dim3(grid_for(Mg, rpb, std::max(bn_grid_cap() / G, 64)), G), dim3(256), 0, s, jp);
-        else DR_LAUNCH(bn_train_join_kernel, dim3(grid_for(M, rpb, bn_grid_cap())), dim3(256), 0, s, jp);
+        launch_bn_fwd_join(jp, s);
         return DR_OK;
     }
-    if (G > 1) {                                             // groups: the finalize launch walks the chain, the apply's grid.y = group
-        launch_bn_fwd_finalize(bp, s);
-        if (bp.raw_bf16) DR_LAUNCH((bn_train_apply_kernel<0, 1>), dim3(grid_for(Mg, rpb, std::max(bn_grid_cap() / G, 64)), G), dim3(256), 0, s, bp);
-        else DR_LAUNCH((bn_train_apply_kernel<0, 0>), dim3(grid_for(Mg, rpb, std::max(bn_grid_cap() / G, 64)), G), dim3(256), 0, s, bp);
-    } else if (bp.part_rows <= kBnFuseRows) {                // few partial rows: the apply pass folds them itself
-        if (bp.raw_bf16) DR_LAUNCH((bn_train_apply_kernel<1, 1>), dim3(grid_for(M, rpb, bn_grid_cap())), dim3(256), 0, s, bp);
-        else DR_LAUNCH((bn_train_apply_kernel<1, 0>), dim3(grid_for(M, rpb, bn_grid_cap())), dim3(256), 0, s, bp);
-    } else if (h->bn_lookback) {                             // its first workgroups fold, everybody else looks back
+    if (form == kBnLookback) {
         c.ep_fwd += 1;
         bp.flag = h->bn_flags + 4 * op.conv; bp.flag_target = c.ep_fwd * dr_ceil_div(c.cout, 4);
-        DR_LAUNCH(bn_train_apply_kernel<2>, dim3(grid_for(M, rpb, bn_grid_cap()) + dr_ceil_div(c.cout, 4)), dim3(256), 0, s, bp);
-    } else {
-        launch_bn_fwd_finalize(bp, s);
-        if (bp.raw_bf16) DR_LAUNCH((bn_train_apply_kernel<0, 1>), dim3(grid_for(M, rpb, bn_grid_cap())), dim3(256), 0, s, bp);
-        else DR_LAUNCH((bn_train_apply_kernel<0, 0>), dim3(grid_for(M, rpb, bn_grid_cap())), dim3(256), 0, s, bp);
     }
+    if (launch_bn_fwd_apply(bp, form, s)) DR_FAIL(h, DR_E_STATE, "conv %s: the look-back BatchReNorm apply reads fp32 only", c.name.c_str());
     return DR_OK;
 }
 
@@ -685,9 +663,6 @@ int backward_conv(dr_handle* h, const Op& op, int B, hipStream_t s) {
         const int G_ = h->groups;                                     // micro-batch groups: per-group sums and coefficients
         const long Mg = M / G_;
         bp.groups = G_; bp.Mg = Mg; bp.fold_stride = (long)h->n_fold; bp.bnc_stride = (long)h->n_bnc;
-        const int rpb = 256 / (raw->cs / 4);
-        // one partial row per workgroup, folded by finalize; measured (tools/bn_bench.py, [40960][256]): 256 workgroups
-        // 22 us, 1024 30 us, 2048 38 us -- one workgroup per CU streams at 3.8 TB/s and keeps the fold short
         if (op.join_role == 1) {                                      // the joined peer's apply pass already reduced (plan_backward)
             if (c.join_rows <= 0) DR_FAIL(h, DR_E_STATE, "conv %s: joined skip branch without its backward sums", c.name.c_str());
             bp.part_rows = c.join_rows;                               // (in stat_part: the peer's dgrad wrote stat_part2 since)
@@ -697,51 +672,29 @@ int backward_conv(dr_handle* h, const Op& op, int B, hipStream_t s) {
             bp.part_rows = c.bst_rows;
             c.bst_rows = 0;
         } else {
-            static const int red_cap = [] { const char* e = getenv("DR_BN_RED_GRID"); const int v = e ? atoi(e) : 0; return v >= 32 ? v : 256; }();
-            const int rows_g = grid_for(Mg, rpb * 8, std::max(red_cap / G_, 32));
-            bp.part_rows = rows_g * G_;
-            if (bp.raw_bf16) DR_LAUNCH(bn_bwd_reduce_kernel<1>, dim3(rows_g, G_), dim3(256), 0, s, bp);
-            else DR_LAUNCH(bn_bwd_reduce_kernel<0>, dim3(rows_g, G_), dim3(256), 0, s, bp);
+            launch_bn_bwd_reduce(bp, s);
         }
         bp.rows_per_group = bp.part_rows / G_;
-        if (op.join_role) {                                           // joined projection residual: always the finalize-launch form
-            if (bp.part_rows % G_) DR_FAIL(h, DR_E_STATE, "conv %s: %d backward rows for %d groups", c.name.c_str(), bp.part_rows, G_);
-            if (bp.raw_bf16 || bp.dout_bf16 || bp.draw_bf16 || h->bn_lookback) DR_FAIL(h, DR_E_STATE, "conv %s: joined BatchReNorm branches need the fp32 path", c.name.c_str());
-            launch_bn_bwd_finalize(bp, s);
-            const dim3 grid = G_ > 1 ? dim3(grid_for(Mg, rpb, std::max(bn_grid_cap() / G_, 64)), G_) : dim3(grid_for(M, rpb, bn_grid_cap()));
-            if (op.join_role == 1) {
-                DR_LAUNCH((bn_bwd_apply_kernel<0, 0>), grid, dim3(256), 0, s, bp);
-            } else {
-                ConvLayer& cs = h->convs[h->ops[op.join_peer].conv];
-                const int rows = (int)(grid.x * grid.y);
-                if (cs.raw->cs != raw->cs || cs.raw->is_bf16 || (size_t)rows * 2 * c.cout > h->n_stat_part)
-                    DR_FAIL(h, DR_E_STATE, "conv %s: joined skip branch with another layout, or %d partial rows beyond the buffer", c.name.c_str(), rows);
-                BnBwdJoinParams jp{};
-                jp.b = bp;
-                jp.raw2 = cs.raw->p; jp.scale2 = h->fold + cs.fold_off; jp.shift2 = h->fold + cs.fold_off + cs.cout; jp.bnc2 = h->bnc + cs.bnc_off;
-                jp.part2 = h->stat_part_l[op.lane];                   // (this layer's own rows there, if any, were folded by the finalize above)
-                DR_LAUNCH(bn_bwd_join_kernel, grid, dim3(256), 0, s, jp);
-                cs.join_rows = rows;
-            }
-        } else if (G_ > 1) {
-            if (bp.part_rows % G_) DR_FAIL(h, DR_E_STATE, "conv %s: %d backward rows for %d groups", c.name.c_str(), bp.part_rows, G_);
-            launch_bn_bwd_finalize(bp, s);
-            if (bp.raw_bf16 && bp.dout_bf16) DR_LAUNCH((bn_bwd_apply_kernel<0, 1, 1>), dim3(grid_for(Mg, rpb, std::max(bn_grid_cap() / G_, 64)), G_), dim3(256), 0, s, bp);
-            else if (bp.raw_bf16) DR_LAUNCH((bn_bwd_apply_kernel<0, 1>), dim3(grid_for(Mg, rpb, std::max(bn_grid_cap() / G_, 64)), G_), dim3(256), 0, s, bp);
-            else DR_LAUNCH((bn_bwd_apply_kernel<0, 0>), dim3(grid_for(Mg, rpb, std::max(bn_grid_cap() / G_, 64)), G_), dim3(256), 0, s, bp);
-        } else if (bp.part_rows <= kBnFuseRows) {
-            if (bp.raw_bf16 && bp.dout_bf16) DR_LAUNCH((bn_bwd_apply_kernel<1, 1, 1>), dim3(grid_for(M, rpb, bn_grid_cap())), dim3(256), 0, s, bp);
-            else if (bp.raw_bf16) DR_LAUNCH((bn_bwd_apply_kernel<1, 1>), dim3(grid_for(M, rpb, bn_grid_cap())), dim3(256), 0, s, bp);
-            else DR_LAUNCH((bn_bwd_apply_kernel<1, 0>), dim3(grid_for(M, rpb, bn_grid_cap())), dim3(256), 0, s, bp);
-        } else if (h->bn_lookback) {
+        if (bp.part_rows % G_) DR_FAIL(h, DR_E_STATE, "conv %s: %d backward rows for %d groups", c.name.c_str(), bp.part_rows, G_);
+        const BnForm form = bn_form(bp.part_rows, G_, op.join_role != 0, h->bn_lookback);
+        if (op.join_role && (bp.raw_bf16 || bp.dout_bf16 || bp.draw_bf16 || h->bn_lookback))
+            DR_FAIL(h, DR_E_STATE, "conv %s: joined BatchReNorm branches need the fp32 path", c.name.c_str());
+        if (form == kBnLookback) {
             c.ep_bwd += 1;
             bp.flag = h->bn_flags + 4 * op.conv + 2; bp.flag_target = c.ep_bwd * dr_ceil_div(c.cout, 4);
-            DR_LAUNCH(bn_bwd_apply_kernel<2>, dim3(grid_for(M, rpb, bn_grid_cap()) + dr_ceil_div(c.cout, 4)), dim3(256), 0, s, bp);
-        } else {
+        }
+        if (op.join_role == 2) {                                      // also reduces the skip conv's sums, for its finalize + apply
+            ConvLayer& cs = h->convs[h->ops[op.join_peer].conv];
+            if (cs.raw->cs != raw->cs || cs.raw->is_bf16) DR_FAIL(h, DR_E_STATE, "conv %s: joined skip branch with another layout", c.name.c_str());
             launch_bn_bwd_finalize(bp, s);
-            if (bp.raw_bf16 && bp.dout_bf16) DR_LAUNCH((bn_bwd_apply_kernel<0, 1, 1>), dim3(grid_for(M, rpb, bn_grid_cap())), dim3(256), 0, s, bp);
-            else if (bp.raw_bf16) DR_LAUNCH((bn_bwd_apply_kernel<0, 1>), dim3(grid_for(M, rpb, bn_grid_cap())), dim3(256), 0, s, bp);
-            else DR_LAUNCH((bn_bwd_apply_kernel<0, 0>), dim3(grid_for(M, rpb, bn_grid_cap())), dim3(256), 0, s, bp);
+            BnBwdJoinParams jp{};
+            jp.b = bp;
+            jp.raw2 = cs.raw->p; jp.scale2 = h->fold + cs.fold_off; jp.shift2 = h->fold + cs.fold_off + cs.cout; jp.bnc2 = h->bnc + cs.bnc_off;
+            jp.part2 = h->stat_part_l[op.lane];                       // (this layer's own rows there, if any, were folded by the finalize above)
+            cs.join_rows = launch_bn_bwd_join(jp, h->n_stat_part, s);
+            if (cs.join_rows <= 0) DR_FAIL(h, DR_E_STATE, "conv %s: the skip branch's partial rows go beyond the statistics buffer", c.name.c_str());
+        } else if (launch_bn_bwd_apply(bp, form, s)) {
+            DR_FAIL(h, DR_E_STATE, "conv %s: no BatchReNorm backward apply for this storage", c.name.c_str());
         }
         G = scratch; g_cs = raw->cs; g_coff = 0;
     } else if (c.bst_rows > 0) {

@@ -995,6 +995,102 @@ __global__ __launch_bounds__(256) void bn_bwd_join_kernel(const BnBwdJoinParams 
     bn_bwd_partial_row(a, b, c4n, p.C, q.part2, part_rows, part_row);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Host launchers of the train-mode BatchReNorm passes: the ONE definition of a layer's form, of every grid and of the
+// <MODE, R16, D16> instance launched.  The executors (train_exec.inc: run_conv_train, backward_conv), dr_read_activation and
+// the debug hooks fill the parameters and call these; nothing else launches the kernels above.
+// ------------------------------------------------------------------------------------------------
+// The form of a layer's apply pass = the kernels' MODE.
+enum BnForm { kBnFinalize = 0, kBnFused = 1, kBnLookback = 2 };
+// BatchReNorm layers with at most this many partial rows fold them inside the apply kernels.
+// (80, which would cover the 8x8-pixel layers on the split-K kernel's 32-row tiles, measured slower: 1767 vs 1782 crops/s.)
+constexpr int kBnFuseRows = 48;
+// Micro-batch groups (the finalize launch walks their chain, the apply's grid.y = group) and joined projection residuals: always the
+// finalize launch; few partial rows: the apply pass folds them itself; DR_BN_LOOKBACK=1: its first workgroups fold, everybody else
+// looks back.
+inline BnForm bn_form(int part_rows, int groups, bool joined, bool lookback) {
+    if (joined || groups > 1) return kBnFinalize;
+    if (part_rows <= kBnFuseRows) return kBnFused;
+    return lookback ? kBnLookback : kBnFinalize;
+}
+// Workgroup cap of the BatchReNorm streaming passes: 512 = two per CU, each thread keeping kBnRows 16-byte loads per tensor in
+// flight.  Measured on the training step (DR_BN_GRID overrides): 8192 -> 1808 crops/s, 4096 -> 1874, 2048 (round 1) -> 1931,
+// 1024 -> 1964, 768 -> 1967, 512 -> 1969-1974, 384 -> 1954, 256 -> 1957; eight rows in flight instead of four: no difference.
+inline int bn_grid_cap() {
+    static const int cap = [] { const char* e = getenv("DR_BN_GRID"); const int v = e ? atoi(e) : 0; return v >= 64 ? v : 512; }();
+    return cap;
+}
+// ... and of the backward reduce pass: one partial row per workgroup, folded by finalize; measured (tools/bn_bench.py,
+// [40960][256]): 256 workgroups 22 us, 1024 30 us, 2048 38 us -- one workgroup per CU streams at 3.8 TB/s and keeps the fold short
+inline int bn_reduce_cap() {
+    static const int cap = [] { const char* e = getenv("DR_BN_RED_GRID"); const int v = e ? atoi(e) : 0; return v >= 32 ? v : 256; }();
+    return cap;
+}
+// Grid of the apply and join passes over M rows of channel stride raw_cs; groups > 1: grid.y = micro-batch group, M / groups rows each.
+inline dim3 bn_apply_grid(long M, int raw_cs, int groups) {
+    const int rpb = 256 / (raw_cs / 4);
+    if (groups > 1) return dim3(grid_for(M / groups, rpb, std::max(bn_grid_cap() / groups, 64)), groups);
+    return dim3(grid_for(M, rpb, bn_grid_cap()));
+}
+inline dim3 bn_reduce_grid(long M, int raw_cs, int groups) {
+    const int G = groups > 1 ? groups : 1;
+    return dim3(grid_for(M / G, 256 / (raw_cs / 4) * 8, std::max(bn_reduce_cap() / G, 32)), G);
+}
+// Partial rows per group of a moments_kernel launch (the stem; groups the conv tiles cannot be cut at): grid (this, G), Mg rows each.
+inline int bn_moments_rows(long Mg, int G) { return grid_for(Mg / 8, 1, 1024 / G); }
+
+// Forward apply in the given form: the finalize launch where the form needs it (finalize = false: the coefficients of an earlier one
+// are in place -- dr_read_activation), then the apply instance.  kBnLookback: the caller has set flag / flag_target; fp32 storage
+// only (nonzero return, nothing launched).
+inline int launch_bn_fwd_apply(BnTrainParams& p, BnForm form, hipStream_t s, bool finalize = true) {
+    dim3 grid = bn_apply_grid(p.M, p.raw_cs, p.groups);
+    if (form == kBnLookback && p.raw_bf16) return -1;
+    if (form == kBnLookback) grid.x += dr_ceil_div(p.C, 4);   // [producers | streaming workgroups]
+    if (form == kBnFinalize && finalize) launch_bn_fwd_finalize(p, s);
+    if (form == kBnLookback) DR_LAUNCH(bn_train_apply_kernel<2>, grid, dim3(256), 0, s, p);
+    else if (form == kBnFused && p.raw_bf16) DR_LAUNCH((bn_train_apply_kernel<1, 1>), grid, dim3(256), 0, s, p);
+    else if (form == kBnFused) DR_LAUNCH((bn_train_apply_kernel<1, 0>), grid, dim3(256), 0, s, p);
+    else if (p.raw_bf16) DR_LAUNCH((bn_train_apply_kernel<0, 1>), grid, dim3(256), 0, s, p);
+    else DR_LAUNCH((bn_train_apply_kernel<0, 0>), grid, dim3(256), 0, s, p);
+    return 0;
+}
+// The last conv of a joined projection residual, after the finalize launches of both branches.
+inline void launch_bn_fwd_join(const BnJoinParams& q, hipStream_t s) {
+    DR_LAUNCH(bn_train_join_kernel, bn_apply_grid(q.b.M, q.b.raw_cs, q.b.groups), dim3(256), 0, s, q);
+}
+// Backward reduce: one partial row per workgroup, p.part_rows of them (blocks > 0: that many instead, one batch -- dr_dbg_bn_bench).
+inline void launch_bn_bwd_reduce(BnBwdParams& p, hipStream_t s, int blocks = 0) {
+    const dim3 grid = blocks > 0 ? dim3(blocks) : bn_reduce_grid(p.M, p.raw_cs, p.groups);
+    p.part_rows = (int)(grid.x * grid.y);
+    if (p.raw_bf16) DR_LAUNCH(bn_bwd_reduce_kernel<1>, grid, dim3(256), 0, s, p);
+    else DR_LAUNCH(bn_bwd_reduce_kernel<0>, grid, dim3(256), 0, s, p);
+}
+// Backward apply in the given form, like launch_bn_fwd_apply (finalize = false: dr_dbg_bn_bench times the apply launch alone).
+// A bf16-stored dOut comes with a bf16-stored raw output only.
+inline int launch_bn_bwd_apply(BnBwdParams& p, BnForm form, hipStream_t s, bool finalize = true) {
+    dim3 grid = bn_apply_grid(p.M, p.raw_cs, p.groups);
+    if ((p.dout_bf16 && !p.raw_bf16) || (form == kBnLookback && p.raw_bf16)) return -1;
+    if (form == kBnLookback) grid.x += dr_ceil_div(p.C, 4);
+    if (form == kBnFinalize && finalize) launch_bn_bwd_finalize(p, s);
+    if (form == kBnLookback) DR_LAUNCH(bn_bwd_apply_kernel<2>, grid, dim3(256), 0, s, p);
+    else if (form == kBnFused && p.dout_bf16) DR_LAUNCH((bn_bwd_apply_kernel<1, 1, 1>), grid, dim3(256), 0, s, p);
+    else if (form == kBnFused && p.raw_bf16) DR_LAUNCH((bn_bwd_apply_kernel<1, 1>), grid, dim3(256), 0, s, p);
+    else if (form == kBnFused) DR_LAUNCH((bn_bwd_apply_kernel<1, 0>), grid, dim3(256), 0, s, p);
+    else if (p.dout_bf16) DR_LAUNCH((bn_bwd_apply_kernel<0, 1, 1>), grid, dim3(256), 0, s, p);
+    else if (p.raw_bf16) DR_LAUNCH((bn_bwd_apply_kernel<0, 1>), grid, dim3(256), 0, s, p);
+    else DR_LAUNCH((bn_bwd_apply_kernel<0, 0>), grid, dim3(256), 0, s, p);
+    return 0;
+}
+// The last conv of a joined projection residual, after its finalize launch: returns the partial rows of the skip conv's sums it
+// wrote to q.part2 (the peer's join_rows), or 0 with nothing launched when they exceed part2_elems doubles.
+inline int launch_bn_bwd_join(const BnBwdJoinParams& q, size_t part2_elems, hipStream_t s) {
+    const dim3 grid = bn_apply_grid(q.b.M, q.b.raw_cs, q.b.groups);
+    const int rows = (int)(grid.x * grid.y);
+    if ((size_t)rows * 2 * q.b.C > part2_elems) return 0;
+    DR_LAUNCH(bn_bwd_join_kernel, grid, dim3(256), 0, s, q);
+    return rows;
+}
+
 // bias convs: g(m,c) = dOut(m,c) * factor * [out(m,c) > 0 if relu]  -> dense scratch (stride gcs), pads zero
 __global__ __launch_bounds__(256) void act_bwd_kernel(View dout, View out, int relu, float factor, float* g, int gcs, long M,
                                                       int C) {

@@ -3,8 +3,10 @@ runs conv + statistics + finalize and no apply pass, the module's last conv form
 forward apply and the skip conv's backward sums in its backward apply (train_kernels.h: bn_train_join_kernel, bn_bwd_join_kernel;
 train_exec.inc: plan_backward).  ``DR_BN_JOIN=0`` keeps the two-pass form.
 
-* kernel level, through ``dr_dbg_bn_join``: both forms against an fp64 autograd of the pair (1e-5 of each tensor's max, the bound of
-  tests/test_bn_layer.py), and the joined output bit-equal to the two-pass one;
+* kernel level, through ``dr_dbg_bn_join``, which fills the parameters and calls the launchers the executors call (train_kernels.h:
+  bn_form, launch_bn_fwd_apply / _join, launch_bn_bwd_reduce / _apply / _join -- form, grids and kernel instances are theirs): both
+  forms against an fp64 autograd of the pair (1e-5 of each tensor's max, the bound of tests/test_bn_layer.py), and the joined output
+  bit-equal to the two-pass one;
 * network level: one training step, joined against two-pass (losses and module outputs bit-equal) and against the oracle's fp64
   autograd taking the engine's switches (the bar of tests/test_train_parity.py's switch-free gradient test);
 * ``dr_read_activation`` of a joined skip conv, which the forward no longer stores;
@@ -246,13 +248,19 @@ def test_training_step_joined_against_two_pass_and_the_fp64_oracle(request, back
     h_t.close()
 
 
-def test_read_activation_of_a_joined_skip_conv(be, monkeypatch):
+@pytest.mark.parametrize('backend, groups', [pytest.param('emu', 1), pytest.param('gpu', 1, marks=pytest.mark.gpu),
+                                             pytest.param('gpu', 2, marks=pytest.mark.gpu)])
+def test_read_activation_of_a_joined_skip_conv(request, backend, groups, monkeypatch):
     """The training forward does not store a joined skip conv's activation; dr_read_activation rebuilds it on request: bit-equal to
     max(raw * scale + shift, 0) from "#raw" and "#fold" -- one rounding on the GPU (the kernels' fused multiply-add: the product of
-    two fp32 values is exact in fp64), two on the emulator (built without contraction) -- and to what the two-pass form stored."""
+    two fp32 values is exact in fp64), two on the emulator (built without contraction) -- and to what the two-pass form stored.
+    Two micro-batch groups (B = 16, the smallest window the executors accept: see the training-step test above): the rebuilding
+    launch takes the executors' grouped grid, "#fold" is [G][2][C] and the rows of group g take the coefficients of group g."""
     from oracle.graph import conv_specs
     from tests.test_train_parity import _case
-    B = 1 if be.name == 'emu' else 2
+    be = request.getfixturevalue(backend)
+    B = 16 if groups == 2 else 1 if be.name == 'emu' else 2
+    Bg = B // groups
     cfg, params, ndm, poses, cfgs, coms = _case(1, 64, 4, B)
     specs = {c.name: c for c in conv_specs(cfg)}
     got = {}
@@ -261,6 +269,8 @@ def test_read_activation_of_a_joined_skip_conv(be, monkeypatch):
         h = be.handle(cfg, B, training=True)
         h.load_params(params)
         h.call('dr_finalize_params', be.stream)
+        if groups > 1:
+            h.call('dr_set_groups', groups)
         d_dm = be.dev(ndm)
         h.call('dr_forward_train', B, be.ptr(d_dm), 0, None, C.c_uint64(0), be.stream)
         be.sync()
@@ -271,14 +281,18 @@ def test_read_activation_of_a_joined_skip_conv(be, monkeypatch):
             got[(cs, join)] = y
             if join:
                 raw = be.read_activation(h, cs + '#raw', shape)
-                fold = be.read_activation(h, cs + '#fold', (2 * c.cout,))
-                if be.name == 'emu':
-                    want = np.maximum(raw * fold[:c.cout] + fold[c.cout:], np.float32(0))
-                else:
-                    want = np.maximum((raw.astype(np.float64) * fold[:c.cout].astype(np.float64) + fold[c.cout:].astype(np.float64))
-                                      .astype(np.float32), np.float32(0))
-                assert want.dtype == np.float32 and (want > 0).any()
-                np.testing.assert_array_equal(y, want, err_msg=cs)
+                fold = be.read_activation(h, cs + '#fold', (groups * 2 * c.cout,)).reshape(groups, 2, c.cout)
+                for g in range(groups):
+                    sl = slice(g * Bg, (g + 1) * Bg)
+                    if be.name == 'emu':
+                        want = np.maximum(raw[sl] * fold[g, 0] + fold[g, 1], np.float32(0))
+                    else:
+                        want = np.maximum((raw[sl].astype(np.float64) * fold[g, 0].astype(np.float64) + fold[g, 1].astype(np.float64))
+                                          .astype(np.float32), np.float32(0))
+                    assert want.dtype == np.float32 and (want > 0).any()
+                    np.testing.assert_array_equal(y[sl], want, err_msg='%s, group %d' % (cs, g))
+                if groups > 1:
+                    assert not np.array_equal(fold[0], fold[1]), cs       # (the groups' coefficients do differ: the slices above matter)
         h.close()
     for cs, _ in _projection_pairs(cfg):
         np.testing.assert_array_equal(got[(cs, True)], got[(cs, False)], err_msg=cs)

@@ -1,6 +1,7 @@
 """Kernel-level pin of the train-mode BatchReNorm path: ONE conv -> BatchReNorm(train) -> ReLU (+ residual) layer through
-``dr_dbg_bn_layer`` -- the executors' own launch logic (conv epilogue statistics, finalize or fused fold, apply; backward
-reduce or the consumer-dgrad-fused sums, finalize, apply) -- against an fp64 autograd of the same layer
+``dr_dbg_bn_layer`` -- the launchers the executors call (train_kernels.h: bn_form, launch_bn_fwd_apply, launch_bn_bwd_reduce,
+launch_bn_bwd_apply: the form, every grid and the kernel instance are theirs; conv epilogue statistics, finalize or fused fold,
+apply; backward reduce or the consumer-dgrad-fused sums, finalize, apply) -- against an fp64 autograd of the same layer
 (``network/slim/ops.py:130-171``: biased moments, eps inside the sqrt, r / d clipped and stop-gradient, zero-debiased
 moving averages).  Tolerance 1e-5 of each tensor's max (the whole-network tests accept 6e-2: a 1 % error in
 ``mean(g * yhat)`` would pass there and fails here).  ``[emu]`` on CPU fibers (small shapes), ``[gpu]`` on an MI355X.
