@@ -65,6 +65,18 @@ STEP_REPORT_FIELDS = {'param_stats': (lambda V, E: (V, 4), False), 'grad_stats':
 STEP_REPORT_MAX_EDGES = 2048
 
 
+class DrPanel(C.Structure):
+    """include/densereg.h: struct dr_panel -- one panel of dr_render_panels."""
+    _fields_ = [('src_dev', C.c_void_p)] + [(n, C.c_int32) for n in ('src_h', 'src_w', 'src_c', 'channel', 'kind')] + [
+        ('pts_dev', C.c_void_p)] + [(n, C.c_int32) for n in ('num_pts', 'pts_space', 'pts_hw', 'skeleton')] + [('cfg_dev', C.c_void_p)]
+
+
+PANEL_JET, PANEL_GREYS, PANEL_UM_XY = 0, 1, 2
+PTS_NONE, PTS_UVD, PTS_XYZ_MM = 0, 1, 2
+SKEL_NONE, SKEL_ICVL, SKEL_NYU, SKEL_MSRA = 0, 1, 2, 3
+RENDER_MAX_PANELS = 16
+
+
 class KernelStat(C.Structure):
     _fields_ = [('name', C.c_char * 64), ('launches', C.c_int64), ('total_ms', C.c_double), ('flops', C.c_double),
                 ('bytes', C.c_double)]
@@ -145,6 +157,8 @@ SIGNATURES = {
     'dr_crop_from_pose': (_i, [_i, _vp, _i, _i, _vp, _i, _vp, _i, C.c_float, _i, _vp, _vp, _vp, _vp]),
     'dr_crop_from_bbx': (_i, [_i, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     'dr_data_aug': (_i, [_i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'dr_render_panels': (_i, [_i, C.POINTER(DrPanel), _i, _i, _vp, _vp]),
+    'dr_colormap': (_i, [_i, _vp]),
     'dr_profile_enable': (_i, [_vp, _i]),
     'dr_profile_read': (_i, [_vp, C.POINTER(KernelStat), _i, C.POINTER(_i)]),
     'dr_profile_detail': (_i, [_vp, C.POINTER(KernelStat), _i, C.POINTER(_i)]),
@@ -168,7 +182,8 @@ DEBUG_SIGNATURES = {
     'dr_dbg_mfma_peak': (_i, [_i, _i, _i, C.POINTER(C.c_float)]),
     'dr_dbg_bn_layer': (_i, [C.POINTER(DbgBnArgs), _vp]),
     'dr_dbg_bn_join': (_i, [C.POINTER(DbgBnJoinArgs), _vp]),
-    'dr_dbg_maxpool': (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    'dr_dbg_vis_sin': (_i, [_vp, _i, _vp, _vp]),
+    'dr_dbg_maxpool':(_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     'dr_dbg_act_dgrad': (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, C.c_float, _vp, _vp, _vp]),
     'dr_dbg_conv2d': (_i, [_i, _i, _i, _i, _i, _i, _fp, _i, _fp, _fp, _fp, _i, _fp, _i, _fp, C.c_float, _fp, _i, _fp, _vp]),
 }

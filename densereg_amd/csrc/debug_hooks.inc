@@ -683,3 +683,14 @@ extern "C" int dr_dbg_force_bf16(int on) {
     g_dbg_bf16 = on ? 1 : 0;
     return DR_OK;
 }
+
+// render.h's sine polynomial alone: y[i] = vis_sin(x[i])
+__global__ __launch_bounds__(256) void dbg_vis_sin_kernel(const float* x, int n, float* y) {
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) y[i] = vis_sin(x[i]);
+}
+extern "C" int dr_dbg_vis_sin(const float* x, int n, float* y, dr_stream stream) {
+    if (!x || !y || n < 1) return DR_E_INVALID;
+    DR_LAUNCH(dbg_vis_sin_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, x, n, y);
+    std::string m;
+    return rt::last_error(&m) ? DR_E_DEVICE : DR_OK;
+}

@@ -23,6 +23,7 @@
 #include "loss_report.h"
 #include "step_report.h"
 #include "vote.h"
+#include "render.h"
 
 using namespace dr;
 
@@ -1314,6 +1315,52 @@ int dr_data_aug(int B, const float* dms, int H, int W, const float* pose, int J,
     DR_LAUNCH(data_aug_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, p);
     std::string m;
     return rt::last_error(&m) ? DR_E_DEVICE : DR_OK;
+}
+
+// ---- image report: handle-free, one workgroup per (panel, crop) (render.h) -------------------------------------
+static_assert(DR_PANEL_JET == kPanelJet && DR_PANEL_GREYS == kPanelGreys && DR_PANEL_UM_XY == kPanelUmXy, "render.h panel kinds");
+static_assert(DR_PTS_NONE == kPtsNone && DR_PTS_UVD == kPtsUvd && DR_PTS_XYZ_MM == kPtsXyzMm, "render.h point spaces");
+static_assert(DR_SKEL_NONE == kSkelNone && DR_SKEL_ICVL == kSkelIcvl && DR_SKEL_NYU == kSkelNyu && DR_SKEL_MSRA == kSkelMsra, "render.h skeletons");
+
+int dr_render_panels(int B, const struct dr_panel* panels, int num_panels, int out_hw, uint8_t* rgb, dr_stream stream) {
+    if (!panels || !rgb || B < 1 || num_panels < 1 || num_panels > kRenderMaxPanels) return DR_E_INVALID;
+    if (out_hw < 4 || out_hw > kRenderMaxOut || (out_hw & 3) || ((uintptr_t)rgb & 3)) return DR_E_INVALID;
+    RenderParams p{};
+    int max_pix = 0;
+    for (int i = 0; i < num_panels; ++i) {
+        const dr_panel& a = panels[i];
+        if (!a.src_dev || a.src_h < 1 || a.src_w < 1 || a.src_c < 1 || a.channel < 0) return DR_E_INVALID;
+        if (a.kind != DR_PANEL_JET && a.kind != DR_PANEL_GREYS && a.kind != DR_PANEL_UM_XY) return DR_E_INVALID;
+        if (a.kind == DR_PANEL_UM_XY ? (long)3 * a.channel + 2 >= a.src_c : a.channel >= a.src_c) return DR_E_INVALID;
+        if (a.pts_space != DR_PTS_NONE) {
+            if (a.pts_space != DR_PTS_UVD && a.pts_space != DR_PTS_XYZ_MM) return DR_E_INVALID;
+            if (!a.pts_dev || a.num_pts < 1 || a.num_pts > kRenderMaxPts || a.pts_hw <= 0) return DR_E_INVALID;
+            if (a.pts_space == DR_PTS_XYZ_MM && !a.cfg_dev) return DR_E_INVALID;
+            if (a.skeleton < DR_SKEL_NONE || a.skeleton > DR_SKEL_MSRA) return DR_E_INVALID;
+            if (a.skeleton != DR_SKEL_NONE && render_skel_joints(a.skeleton) != a.num_pts) return DR_E_INVALID;
+        }
+        if ((long)a.src_h * a.src_w > kRenderMaxPix) return DR_E_UNSUPPORTED;
+        if ((long)B * a.src_h * a.src_w * a.src_c >= (1l << 31)) return DR_E_INVALID;
+        max_pix = std::max(max_pix, a.src_h * a.src_w);
+        p.panel[i] = RenderPanel{a.src_dev, a.src_h, a.src_w, a.src_c, a.channel, a.kind,
+                                 a.pts_space != DR_PTS_NONE ? a.pts_dev : nullptr, a.pts_space != DR_PTS_NONE ? a.num_pts : 0, a.pts_space,
+                                 a.pts_space != DR_PTS_NONE ? a.pts_hw : 1, a.pts_space != DR_PTS_NONE ? a.skeleton : DR_SKEL_NONE, a.cfg_dev};
+    }
+    p.num_panels = num_panels; p.out_hw = out_hw; p.rgb = rgb;
+    const size_t lds = render_lds_bytes(max_pix);
+    if (lds > 64 * 1024 && !rt::allow_dyn_lds((const void*)render_kernel, render_lds_bytes(kRenderMaxPix))) return DR_E_DEVICE;
+    DR_LAUNCH(render_kernel, dim3(num_panels, B), dim3(256), lds, (hipStream_t)stream, p);
+    std::string m;
+    return rt::last_error(&m) ? DR_E_DEVICE : DR_OK;
+}
+
+int dr_colormap(int kind, uint8_t* host_lut) {
+    if (!host_lut || (kind != DR_PANEL_JET && kind != DR_PANEL_GREYS)) return DR_E_INVALID;
+    for (int i = 0; i < 256; ++i) {
+        const uint32_t c = kRenderLutHost[kind == DR_PANEL_GREYS ? 1 : 0][i];
+        host_lut[3 * i] = (uint8_t)c; host_lut[3 * i + 1] = (uint8_t)(c >> 8); host_lut[3 * i + 2] = (uint8_t)(c >> 16);
+    }
+    return DR_OK;
 }
 
 int dr_png_unfilter(const uint8_t* filtered, int height, int row_bytes, int bpp, uint8_t* out) {

@@ -1,5 +1,6 @@
 // pose_math.h -- the crop camera, the point cloud and the training targets: ONE definition each, shared by loss_kernel
-// (train_kernels.h), loss_report_body (loss_report.h) and the candidate block of vote_body (vote.h).  fp32 in the reference's op order
+// (train_kernels.h), loss_report_body (loss_report.h), the candidate block and the uvd report of vote_body (vote.h) and the overlay
+// points of render_kernel (render.h).  fp32 in the reference's op order
 // with contraction off (data/preprocess.py:176-242, hourglass_um_crop_tiny.py:338-346; oracle/pose.py make_targets restates it).
 // Pure: values (and pointers to a crop's few label floats) in, values out; every caller keeps its own thread geometry, map loads,
 // reductions and stores.
@@ -18,6 +19,16 @@ constexpr float kOffsetNear = 1e-2f;       // a pixel carries unit offsets when 
 struct MapCam { float fx, fy, cx, cy; };                 // the crop camera at map resolution
 struct CloudPoint { float zz, X, Y, Z; };                // depth in mm; position relative to the centre of mass, normalised
 struct PoseTargets { float gt_hm, gt_hm3, ux, uy, uz; };
+struct Uvd { float u, v, d; };                           // a point in mm projected into an image: pixels and depth
+
+// xyz2uvd_op with a camera cfg6 = fx, fy, cx, cy, w, h, unscaled (data/util.py:20 _pro): u = (x*fx)/z + cx, v = (y*fy)/z + cy, d = z.
+// The vote report's uvd joints (vote.h) and the image report's overlay points (render.h).
+__device__ __forceinline__ Uvd project_uvd(const float* cfg6, float x, float y, float z) {
+#pragma clang fp contract(off)
+    const float u = (x * cfg6[0]) / z + cfg6[2];
+    const float v = (y * cfg6[1]) / z + cfg6[3];
+    return {u, v, z};
+}
 
 // cfg6 = fx, fy, cx, cy, w, h of the crop camera; (w, h) = the map's size
 __device__ __forceinline__ MapCam map_cam(const float* cfg6, int w, int h) {

@@ -289,12 +289,11 @@ __device__ __forceinline__ void vote_body(const VoteParams& p, const VoteReport&
             }
             if (lane == 0) rep.mass[(long)b * J + j] = ss;
         }
-        // xyz2uvd_op with the crop's own camera, unscaled (data/util.py:20 _pro): u = (x*fx)/z + cx, v = (y*fy)/z + cy, d = z
+        // xyz2uvd_op with the crop's own camera, unscaled: pose_math.h's project_uvd
         if (rep.uvd && lane < 3) {
             const float x = ctr[0] * kPoseScale + cx0, y = ctr[1] * kPoseScale + cy0, z = ctr[2] * kPoseScale + cz0;
-            const float u = (x * cfg[0]) / z + cfg[2];
-            const float v = (y * cfg[1]) / z + cfg[3];
-            rep.uvd[((long)b * J + j) * 3 + lane] = lane == 0 ? u : (lane == 1 ? v : z);
+            const Uvd q = project_uvd(cfg, x, y, z);
+            rep.uvd[((long)b * J + j) * 3 + lane] = lane == 0 ? q.u : (lane == 1 ? q.v : q.d);
         }
     }
 }

@@ -89,6 +89,26 @@ class StepReport(NamedTuple):
         return getattr(self, 'global_' if member == 'global' else member)
 
 
+class Panel(NamedTuple):
+    """One panel of ``Engine.render`` (``struct dr_panel``): channel ``channel`` of the float32 device tensor ``src`` (B,h,w,C) --
+    dense NHWC or a channel-slice view of one -- coloured with ``kind`` ('jet', 'greys', or 'um_xy': the jet panel of _vis_um_xy of
+    joint ``channel`` of an offset map), and optionally ``pts`` (B,N,3) drawn over it: ``pts_space`` 'uvd' (pixels of a
+    ``pts_hw``-sided image) or 'xyz_mm' (projected with ``cfg`` (B,6)); ``skeleton`` None, 'icvl', 'nyu' or 'msra'."""
+    src: torch.Tensor
+    channel: int = 0
+    kind: str = 'jet'
+    pts: Optional[torch.Tensor] = None
+    pts_space: str = 'uvd'
+    pts_hw: int = 0
+    skeleton: Optional[str] = None
+    cfg: Optional[torch.Tensor] = None
+
+
+PANEL_KINDS = {'jet': _lib.PANEL_JET, 'greys': _lib.PANEL_GREYS, 'um_xy': _lib.PANEL_UM_XY}
+PTS_SPACES = {'uvd': _lib.PTS_UVD, 'xyz_mm': _lib.PTS_XYZ_MM}
+SKELETONS = {None: _lib.SKEL_NONE, 'icvl': _lib.SKEL_ICVL, 'nyu': _lib.SKEL_NYU, 'msra': _lib.SKEL_MSRA}
+
+
 def hist_edges(lo: float = 1e-12, hi: float = 1e20, ratio: float = 1.1) -> np.ndarray:
     """The symmetric geometric edge set ``-hi ... -lo, +lo ... +hi`` (float32, strictly ascending): ``2 * ceil(log(hi / lo) /
     log(ratio))`` edges, geometrically spaced from ``lo`` to ``hi`` on either side (buckets about ``ratio`` wide) and one bucket
@@ -291,6 +311,45 @@ class Engine:
         self.h.call('dr_loss_report', B, _p(_f32(dm_norm)), _p(_f32(pose_mm)), _p(_f32(cfg)), _p(_f32(com)), C.byref(c_rep),
                     self._stream())
         return rep
+
+    # ---- image report ---------------------------------------------------------------------------
+    def render(self, panels, out_hw: int = 128) -> torch.Tensor:
+        """The image report (``dr_render_panels``): every ``Panel`` of every crop as RGB8, one launch, no host round trip of the
+        maps.  Returns uint8 ``(B, P, out_hw, out_hw, 3)``; ``out_hw`` a multiple of 4 up to 512; at most 16 panels."""
+        panels = list(panels)
+        if not 1 <= len(panels) <= _lib.RENDER_MAX_PANELS:
+            raise ValueError('render: %d panels (1..%d)' % (len(panels), _lib.RENDER_MAX_PANELS))
+        B = panels[0].src.shape[0]
+        arr, keep = (_lib.DrPanel * len(panels))(), []
+        for c, pn in zip(arr, panels):
+            src = _f32(pn.src if pn.src.dim() == 4 else pn.src.unsqueeze(-1))
+            _, h, w, C_ = src.shape
+            cs = src.stride(2)
+            if not (src.is_cuda and src.shape[0] == B and src.stride(3) == 1 and src.stride(1) == w * cs and src.stride(0) == h * w * cs):
+                raise ValueError('render: a panel source must be a (B,h,w,C) device tensor, NHWC-dense or a channel slice of one')
+            if pn.kind not in PANEL_KINDS or not 0 <= (3 * pn.channel + 2 if pn.kind == 'um_xy' else pn.channel) < C_:
+                raise ValueError('render: kind %r / channel %d of a %d-channel source' % (pn.kind, pn.channel, C_))
+            c.src_dev, c.src_h, c.src_w, c.src_c, c.channel, c.kind = src.data_ptr(), h, w, cs, pn.channel, PANEL_KINDS[pn.kind]
+            keep.append(src)
+            if pn.pts is not None:
+                pts = _f32(pn.pts).reshape(B, -1, 3)
+                c.pts_dev, c.num_pts, c.pts_space, c.pts_hw = _p(pts), pts.shape[1], PTS_SPACES[pn.pts_space], int(pn.pts_hw)
+                c.skeleton, c.cfg_dev = SKELETONS[pn.skeleton], _p(pn.cfg)
+                keep.append(pts)
+        out = self.new(B, len(panels), out_hw, out_hw, 3, dtype=torch.uint8)
+        with torch.cuda.device(self.device):
+            rc = self.lib.dr_render_panels(B, arr, len(panels), int(out_hw), _p(out), self._stream())
+        if rc != _lib.DR_OK:
+            raise _lib.DenseRegError(rc, 'dr_render_panels')
+        return out
+
+    def colormap(self, kind: str) -> np.ndarray:
+        """The compiled-in colour table of 'jet' or 'greys' (``dr_colormap``): uint8 (256, 3)."""
+        lut = np.empty((256, 3), np.uint8)
+        rc = self.lib.dr_colormap(PANEL_KINDS[kind], lut.ctypes.data)
+        if rc != _lib.DR_OK:
+            raise _lib.DenseRegError(rc, 'dr_colormap')
+        return lut
 
     def read_activation(self, scope: str, B: int, shape) -> np.ndarray:
         torch.cuda.synchronize(self.device)

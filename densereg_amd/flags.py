@@ -58,6 +58,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help='train: every N-th optimizer step log the norms of the raw and the clipped gradient, the relative size of the '
                    'update and the clipped / zero shares (dr_step_report), and stop on a non-finite gradient, naming the variable '
                    '(0 = never)')
+    p.add_argument('--image_every', type=int, default=0,
+                   help='every N-th test batch / optimizer step write the image summaries of --debug_level (rendered on the device, '
+                   'dr_render_panels) as <train_dir>/summary/<tag>/<step>_<crop>.png (0 = never)')
     return p
 
 

@@ -157,11 +157,77 @@ class JointDetectionModel(object):
             self.gt_hms, self.gt_hm3s, self.gt_ums = lr.gt_hm, lr.gt_hm3, lr.gt_um
         return xyz
 
+    # the reference's image summaries by --debug_level (:408-432, :487-516)
+    _image_tags = ((1, ('val_pts', 'gt_pts')),
+                   (2, ('gt_hm', 'gt_hm3', 'val_hm', 'val_hm3', 'val_dm', 'val_pts_hm')),
+                   (3, ('gt_xy', 'gt_z', 'val_xy', 'val_z')))
+
+    def summary_images(self, dms, poses, cfgs, coms, level=None, train=False, out_hw=128):
+        """The image summaries of the reference (:399-432 training, :487-516 validation) as ``{tag: uint8 (B,out_hw,out_hw,3)}``,
+        rendered on the device (``Engine.render``): level >= 1 the depth crop in Greys with the voted skeleton (``val_pts``) and the
+        ground truth (``gt_pts``); >= 2 the jet panels of hm / hm3 of joint 0 and their targets, the crop alone (``val_dm``) and the
+        heat-map-only estimate (``val_pts_hm``); >= 3 the offset-angle views of joint 0 (``*_xy`` = _vis_um_xy, ``*_z`` = the z
+        offset; ``gt_z`` shows the TARGET offsets).  ``level`` defaults to ``--debug_level``.
+        ``train=False``: one ``infer_report`` on ``dms``.  ``train=True``: the maps of the most recent forward (``read_maps`` +
+        ``vote_report``), the first three crops only (:379-385), and the tags carry ``tra_`` instead of ``val_`` (``gt_x`` becomes
+        ``tra_gt_x``).  One ``targets`` and one ``render`` call either way; nothing here synchronises."""
+        eng = self.engine
+        level = int(flags.FLAGS.debug_level if level is None else level)
+        tags = [t for lv, ts in self._image_tags if level >= lv for t in ts]
+        if not tags:
+            return {}
+        last = eng.num_stack - 1
+        if train:
+            dms, poses, cfgs, coms = (t[:3].contiguous() for t in (dms, poses, cfgs, coms))
+        B = dms.shape[0]
+        normed = eng.norm_dm(dms, coms)
+        hm = hm3 = um = None
+        if train:
+            hm, hm3, um = eng.read_maps(B, last)
+            _, rep = eng.vote_report(hm, hm3, um, normed, cfgs, coms, fields=('uvd', 'hm_peak'))
+        else:
+            _, rep = eng.infer_report(normed, cfgs, coms, fields=('uvd', 'hm_peak'))
+            if level >= 2:
+                hm, hm3, um = eng.read_maps(B, last)
+        skel = self._dataset.name if {'icvl': 16, 'nyu': 14, 'msra': 21}.get(self._dataset.name) == self._jnt_num else None
+        from ..engine import Panel
+        crop = dms.reshape(B, self._input_height, self._input_width, 1)
+
+        def joints(pts, space, cfg=None):
+            return Panel(crop, 0, 'greys', pts, space, self._input_height, skel, cfg)
+        panels = {'val_pts': joints(rep.uvd, 'uvd'), 'gt_pts': joints(poses, 'xyz_mm', cfgs)}
+        if level >= 2:
+            gt_hm, gt_hm3, gt_um = eng.targets(normed, poses, cfgs, coms, fields=('gt_hm', 'gt_hm3') + (('gt_um',) if level >= 3 else ()))
+            panels.update(gt_hm=Panel(gt_hm), gt_hm3=Panel(gt_hm3), val_hm=Panel(hm), val_hm3=Panel(hm3), val_dm=Panel(crop, 0, 'greys'),
+                          val_pts_hm=joints(rep.hm_uvd_pts, 'uvd'))
+        if level >= 3:
+            panels.update(gt_xy=Panel(gt_um, 0, 'um_xy'), gt_z=Panel(gt_um, 2), val_xy=Panel(um, 0, 'um_xy'), val_z=Panel(um, 2))
+        rgb = eng.render([panels[t] for t in tags], out_hw)
+
+        def name(t):
+            return t if not train else ('tra_' + t[4:] if t.startswith('val_') else 'tra_' + t)
+        return {name(t): rgb[:, i] for i, t in enumerate(tags)}
+
     def loss(self, dms, poses, cfgs, coms, seed=0):
         """(:323-371) one training micro-step's forward + loss; returns the 4 terms hm, hm3, um, reg."""
         normed = self.engine.norm_dm(dms, coms)
         self.engine.forward_train(normed, seed=seed)
         return self.engine.loss(normed, poses, cfgs, coms), normed
+
+
+def write_summary_images(train_dir: str, step: int, images) -> list:
+    """``{tag: uint8 (B,H,W,3)}`` -> ``<train_dir>/summary/<tag>/<step>_<crop>.png``; returns the paths.  Reads the tensors (blocks
+    until their launches are done)."""
+    from ..data.png import encode_png
+    paths = []
+    for tag, t in images.items():
+        d = os.path.join(train_dir, 'summary', tag)
+        os.makedirs(d, exist_ok=True)
+        for crop, img in enumerate(t.cpu().numpy()):
+            paths.append(os.path.join(d, '%d_%d.png' % (step, crop)))
+            with open(paths[-1], 'wb') as f:
+                f.write(encode_png(img))
+    return paths
 
 
 def result_line(name: str, xyz) -> str:
@@ -228,7 +294,9 @@ def train(model: JointDetectionModel, dist=None, log=sys.stdout):
 
     def settle(entry):
         """read a finished window's losses: the asserts and the log line of the reference's loop"""
-        st, t0, losses, n_crops, report = entry
+        st, t0, losses, n_crops, report, images = entry
+        if images and (dist is None or dist.get_rank() == 0):               # --image_every: encoded here, with the window's losses
+            write_summary_images(model.train_dir, st + 1, images)
         if report is not None:
             rstep, rep = report
             gl, n_bad, n_clip, n_zero = rep.global_.tolist(), *rep.global_counts.tolist()       # (blocks until the report's launches are done)
@@ -260,10 +328,13 @@ def train(model: JointDetectionModel, dist=None, log=sys.stdout):
                     torch.cuda.synchronize(model.device)
                 t_steady = time.time()
             window, step_losses = [], []
+            shown = None                                                    # the micro-batch whose crops lead the most recent forward
             for dm, poses, cfgs, coms, _n in host:
                 d_dm, d_pose, d_cfg, d_com = model._t(dm), model._t(poses), model._t(cfgs), model._t(coms)
                 if F.is_aug:                                                # hourglass_um_crop_tiny.py:332-333
                     d_dm, d_pose = preprocess.data_aug(d_dm, d_pose, d_cfg, d_com, generator=aug_rng)
+                if shown is None or model.window_groups == 1:
+                    shown = (d_dm, d_pose, d_cfg, d_com)
                 normed = model.engine.norm_dm(d_dm, d_com)
                 if model.window_groups > 1:                                 # the window runs as one pass once it is complete
                     window.append((normed, d_pose, d_cfg, d_com))
@@ -277,7 +348,10 @@ def train(model: JointDetectionModel, dist=None, log=sys.stdout):
                 losses = torch.stack(step_losses)
             if pending is not None:
                 settle(pending)                                             # window k-1, while window k runs
-            pending = (step, start, losses, F.batch_size * F.sub_batch, trainer.take_step_report() if F.step_report > 0 else None)
+            # --image_every N: the tra_ image summaries of the forward that just ran, queued behind the step (the maps outlive it);
+            # the tensors travel with the window's losses and are encoded in settle(): no synchronisation point here either
+            images = model.summary_images(*shown, train=True) if F.image_every > 0 and (step + 1) % F.image_every == 0 else None
+            pending = (step, start, losses, F.batch_size * F.sub_batch, trainer.take_step_report() if F.step_report > 0 else None, images)
             if F.save_every > 0 and ((step + 1) % F.save_every == 0 or step + 1 == max_steps):   # :170-172
                 settle(pending)                                             # a checkpoint is written after ITS losses were checked
                 pending = None
@@ -336,7 +410,11 @@ def test_model(model: JointDetectionModel, out_path: str, log=sys.stdout):
                 dm, poses, cfgs, coms, names = model._val_dataset.batch(model.rank_batch, step)
             except StopIteration:                                           # a record dataset shorter than exact_num
                 break
-            xyz = model.test(model._t(dm), model._t(poses), model._t(cfgs), model._t(coms)).cpu().numpy()
+            d_dm, d_pose, d_cfg, d_com = model._t(dm), model._t(poses), model._t(cfgs), model._t(coms)
+            images = model.summary_images(d_dm, d_pose, d_cfg, d_com) if F.image_every > 0 and step % F.image_every == 0 else None
+            xyz = model.test(d_dm, d_pose, d_cfg, d_com).cpu().numpy()
+            if images:                                                      # (queued before the batch's own inference, read after it)
+                write_summary_images(model.train_dir, step, images)
             for xyz_val, gt_val, name in zip(xyz, poses, names):
                 max_err.append(Evaluation.maxJntError(xyz_val, gt_val))
                 mean_err.append(Evaluation.meanJntError(xyz_val, gt_val))

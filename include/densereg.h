@@ -286,6 +286,35 @@ struct dr_step_report {
 int dr_step_report(dr_handle* h, float lr, float div, float clip, int64_t step, const struct dr_step_report* report,
                    dr_stream stream);
 
+/* ---- image report (no handle) ---------------------------------------------------------------------- */
+/* The reference's image summaries (hourglass_um_crop_tiny.py:399-432, 487-516 through data/visualization.py), rendered on the
+ * device: float maps and joints in, RGB8 out.  A panel is one channel of a (B,src_h,src_w,src_c) float32 NHWC view (the maps of
+ * dr_read_maps / dr_forward_eval, the targets of dr_targets / dr_loss_report, a depth crop with src_c = 1), at most 16384 pixels,
+ * resampled to out_hw x out_hw by nearest source pixel (sy = y*src_h / out_hw, integer), normalised to its own finite range
+ * per crop, t = (v - lo) / (hi - lo), and coloured LUT[min(255, (int)(t * 256))] with matplotlib's jet or Greys at N = 256 (the
+ * tables of dr_colormap); a non-finite value is drawn white, and t = 0 where no value is finite or hi == lo.  DR_PANEL_UM_XY is
+ * the jet panel of _vis_um_xy (:301-311) of joint `channel` of an offset map (channels 3*channel .. 3*channel + 2).
+ * Optional overlay: num_pts points per crop, pts_dev (B,num_pts,3), as uvd in pixels of a pts_hw-sided image (DR_PTS_UVD: the
+ * uvd of dr_vote_report, its hm_peak scaled to the crop) or as xyz in mm projected with cfg_dev (B,6) (DR_PTS_XYZ_MM: exactly
+ * the projection of dr_vote_report's uvd).  With a skeleton (num_pts must be its joint count: icvl 16, nyu 14, msra 21) the discs,
+ * bones, colours and draw order of figure_joint_skeleton; otherwise white discs.  No anti-aliasing: every output byte is defined
+ * exactly (densereg_amd/csrc/render.h states the sizes and the pixel tests).  (A struct tag, not a typedef, as dr_vote_report.) */
+enum { DR_PANEL_JET = 0, DR_PANEL_GREYS = 1, DR_PANEL_UM_XY = 2 };      /* UM_XY: jet of _vis_um_xy of joint `channel` */
+enum { DR_PTS_NONE = 0, DR_PTS_UVD = 1, DR_PTS_XYZ_MM = 2 };
+enum { DR_SKEL_NONE = 0, DR_SKEL_ICVL = 1, DR_SKEL_NYU = 2, DR_SKEL_MSRA = 3 };
+struct dr_panel {
+    const float* src_dev; int32_t src_h, src_w, src_c, channel, kind;
+    const float* pts_dev; int32_t num_pts, pts_space, pts_hw, skeleton; const float* cfg_dev;
+};
+/* One launch on `stream` of the current device renders all panels of all crops; never synchronises, always a plain launch.
+ * `panels` is host memory, read during the call.  rgb_dev: (B, num_panels, out_hw, out_hw, 3) uint8, 4-byte aligned.
+ * DR_E_INVALID: a null or negative argument, num_panels outside 1..16, out_hw not a positive multiple of 4 or above 512, a
+ * channel out of range (3*channel + 2 >= src_c for DR_PANEL_UM_XY), DR_PTS_XYZ_MM without cfg_dev, a skeleton whose joint
+ * count is not num_pts, more than 64 points, pts_hw <= 0 with points given; DR_E_UNSUPPORTED: a source above 16384 pixels. */
+int dr_render_panels(int B, const struct dr_panel* panels, int num_panels, int out_hw, uint8_t* rgb_dev, dr_stream stream);
+/* Host: the compiled-in colour table of DR_PANEL_JET or DR_PANEL_GREYS, 256 x RGB. */
+int dr_colormap(int kind, uint8_t* host_lut /* 256*3 */);
+
 /* ---- dataset formats: PNG depth frames out of the TFRecord files --------------------------- */
 /* Host: undo the PNG row filters (PNG spec 9.2) of an inflated IDAT stream.  `filtered` = height rows of
  * (1 filter-type byte + row_bytes), bpp = bytes per pixel (3 for NYU's RGB8, 2 for 16-bit grey); out = height*row_bytes

@@ -135,6 +135,10 @@ long dr_dbg_x3h_launches(void);
  * small layers run the several-waves-per-group path. */
 int dr_dbg_bn_finalize_rows(int rows);
 
+/* y[i] = vis_sin(x[i]), i < n: the sine polynomial of the image report (densereg_amd/csrc/render.h) alone.  Device pointers;
+ * one launch on `stream`, no synchronisation. */
+int dr_dbg_vis_sin(const float* x, int n, float* y, dr_stream stream);
+
 /* Force the conv tile of every following launch (-1 = heuristic; ids as in dr_dbg_conv_bench).
  * Process-global; tests use it to check every tile shape against the reference. */
 int dr_dbg_force_tile(int tile);
