@@ -802,7 +802,7 @@ static void free_all(dr_handle* h) {
                     (void*)h->shadow, (void*)h->wp, (void*)h->wpT, (void*)h->wp3, (void*)h->wp3T, (void*)h->fold, (void*)h->bnc,
                     (void*)h->act_arena, (void*)h->grad_arena, (void*)h->scratch, (void*)h->tiny, (void*)h->tiny_ext, (void*)h->zeros,
                     (void*)h->losses, (void*)h->reg_segs, (void*)h->loss_acc, (void*)h->bn_coef, (void*)h->wg_partial, (void*)h->fold_dev, h->pack_dev, h->zero_dev,
-                    (void*)h->g_keep_arena, (void*)h->pool_arg_arena, (void*)h->group_dev, (void*)h->bn_flags, (void*)h->loss_report_ws, h->step_report_ws})
+                    (void*)h->g_keep_arena, (void*)h->pool_arg_arena, (void*)h->group_dev, (void*)h->bn_flags, (void*)h->loss_report_ws, h->step_report_ws, h->vote_ws})
         if (p) rt::dfree(p);
     for (int l = 1; l < DR_MAX_LANES; ++l) {
         if (h->scratch_l[l]) rt::dfree(h->scratch_l[l]);
@@ -967,6 +967,10 @@ int dr_create(const dr_config* cfg, dr_handle** out) {
     }
     alloc_f(h->tiny, MB * h->map_hw * h->map_hw);
     alloc_f(h->tiny_ext, MB * h->map_hw * h->map_hw);
+    if (h->map_hw * h->map_hw > kVoteMaxPix) {              // tiled vote: here, because dr_infer may record its launches into a graph
+        h->vote_ws = rt::dmalloc(MB * cfg->num_jnt * dr_ceil_div(h->map_hw * h->map_hw, kVoteTile) * 5 * sizeof(VoteCand));
+        ok = ok && h->vote_ws;
+    }
     alloc_f(h->losses, 4 * (size_t)kMaxGroups);
     alloc_f(h->zeros, 64);
     if (cfg->training) {
@@ -1617,15 +1621,33 @@ static int vote_impl(dr_handle* h, int B, View hm, View hm3, View um, const floa
     vp.hm = hm; vp.hm3 = hm3; vp.um = um; vp.tiny = tiny; vp.cfg = cfg; vp.com = com; vp.xyz_mm = xyz; vp.xyz_norm = nullptr;
     vp.B = B; vp.h = h->map_hw; vp.w = h->map_hw; vp.J = h->cfg.num_jnt;
     const int npix = vp.h * vp.w;
-    if (npix > kVoteMaxPix) DR_FAIL(h, DR_E_UNSUPPORTED, "vote: map of %d px exceeds the LDS plan", npix);
+    VoteReport vr{};
     if (report) {
-        // vote_report_kernel: the same launch geometry and LDS plan; the caller's struct is copied into the launch arguments here.
-        // Accounted under the vote's kernel id (one more read of hm when the peak is wanted, up to 220 B per joint written).
+        // the caller's struct is copied into the launch arguments here
         vp.xyz_norm = report->xyz_norm_dev;
-        VoteReport vr{};
         vr.uvd = report->uvd_dev; vr.can_idx = report->can_idx_dev; vr.can_score = report->can_score_dev;
         vr.can_pts = report->can_pts_dev; vr.ori_pts = report->ori_pts_dev; vr.can_weight = report->can_weight_dev;
         vr.mass = report->mass_dev; vr.hm_peak = report->hm_peak_dev;
+    }
+    if (npix > kVoteMaxPix) {
+        // Tiled path (end of vote.h): scan + finish, both accounted under the vote's kernel id.  The scan streams the maps once and
+        // writes 5 pairs per (joint, tile); the finish reads them back, gathers at the five pixels and writes what vote_kernel writes.
+        const int T = npix / kVoteTile;
+        if (npix % kVoteTile || T > kVoteMaxTiles || !h->vote_ws)
+            DR_FAIL(h, DR_E_UNSUPPORTED, "vote: map of %d px is not 1..%d whole tiles of %d px", npix, kVoteMaxTiles, kVoteTile);
+        VoteCand* ws = (VoteCand*)h->vote_ws;
+        const double ws_bytes = (double)B * vp.J * T * 5 * sizeof(VoteCand);
+        const dim3 quads(B, dr_ceil_div(vp.J, kVoteJC));
+        {
+            ProfScope ps(h, s, KID_VOTE, 0.0, (double)B * (5.0 * vp.J + 1.0) * npix * 4.0 + ws_bytes);
+            DR_LAUNCH(vote_scan_kernel, dim3(T, quads.y, B), dim3(256), (size_t)kVoteJC * kVoteTile * sizeof(float), s, vp, ws);
+        }
+        ProfScope ps(h, s, KID_VOTE, 0.0, ws_bytes + (double)B * ((vr.hm_peak ? vp.J : 0) * npix * 4.0 + 12.0 * vp.J));
+        if (report) { DR_LAUNCH(vote_finish_kernel<true>, quads, dim3(256), 0, s, vp, vr, (const VoteCand*)ws, T); }
+        else { DR_LAUNCH(vote_finish_kernel<false>, quads, dim3(256), 0, s, vp, vr, (const VoteCand*)ws, T); }
+    } else if (report) {
+        // vote_report_kernel: the same launch geometry and LDS plan.
+        // Accounted under the vote's kernel id (one more read of hm when the peak is wanted, up to 220 B per joint written).
         ProfScope ps(h, s, KID_VOTE, 0.0, (double)B * ((5.0 * vp.J + 1.0 + (vr.hm_peak ? vp.J : 0)) * npix * 4.0 + 12.0 * vp.J));
         DR_LAUNCH(vote_report_kernel, dim3(B, dr_ceil_div(vp.J, kVoteJC)), dim3(256), (size_t)kVoteJC * npix * sizeof(float), s, vp, vr);
     } else {

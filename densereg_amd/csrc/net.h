@@ -217,6 +217,8 @@ struct dr_handle {
     void* step_report_ws = nullptr;                         // dr_step_report: chunk table | variable table | per-chunk partials
                                                             // (step_report.h); built by the first call, the layout never changes
     int step_nchunk = 0, step_nvar = 0;
+    void* vote_ws = nullptr;                                // tiled vote (maps above 4096 px, vote.h): partial candidates
+                                                            // [max_batch][J][T][5]; allocated by dr_create, never inside a graph capture
     const float* dm_in = nullptr;                           // input of the last forward (not owned)
 
     // network outputs per stack (dense-ish tensors)

@@ -23,6 +23,11 @@
 // fetch output" (:464-471, 521-526, 781-784) -- uvd joints, candidates, their point-cloud positions, weights, the heat-map-only peak --
 // and the kernel mass at the final centre, each behind a nullable pointer (struct VoteReport).  Same geometry, LDS plan and xyz bits.
 // The crop camera and the point cloud at a candidate pixel are pose_math.h's map_cam and cloud_point, the functions the loss targets use.
+//
+// Maps above kVoteMaxPix pixels (128x128, in_hw = 512) take the tiled path at the end of this file (vote_scan_kernel +
+// vote_finish_kernel): the same phase 1 and selection rounds per tile of 4096 pixels, a merge of the tiles' top-5 lists, and the same
+// tail.  Everything both paths compute is stated once: vote_before (the order), vote_refine_to_lds (phase 1), vote_top5 (the five
+// rounds), vote_tail (candidates .. stores).
 #pragma once
 #include "dr_platform.h"
 #include "kernels_misc.h"
@@ -55,6 +60,15 @@ struct VoteReport {
 
 constexpr int kVoteJC = 4;         // joints per workgroup (= waves)
 constexpr int kVoteMaxPix = 4096;  // LDS: 4 joints x 4096 px x 4 B = 64 KiB
+constexpr int kVoteTile = kVoteMaxPix;   // tiled path (maps above kVoteMaxPix): pixels per scan workgroup, the same LDS plan
+constexpr int kVoteMaxTiles = 12;        // tiled path: 5 partial candidates per tile, one lane each in the finish wave (5T <= 64)
+constexpr int kVoteNone = 0x7fffffff;    // "no pixel": sorts behind every pixel index
+
+// Tiled path: one partial candidate, workspace [B][J][T][5] written by vote_scan_kernel and read by vote_finish_kernel.
+struct VoteCand {
+    float v;                     // refined heat at px
+    int px;                      // pixel index in the whole map; kVoteNone = the tile had nothing selectable left (NaN only)
+};
 
 // exp(x) for x <= 0 (NaN propagates; x <= -87: 0, the result would be below the smallest normal).  Cody-Waite reduction x = n ln2 + r,
 // degree-5 polynomial in r (Cephes expf / Eigen pexp<float> coefficients), scaling by 2^n through the exponent field; every step
@@ -82,75 +96,78 @@ __device__ __forceinline__ float vote_exp(float x) {
     return q * s;
 }
 
+// THE selection rule (tf.nn.top_k order): (v, i) goes before (bv, bi) when its value is larger or, at equal values, its pixel index
+// is lower.  NaN fails both comparisons and is never selected; (-INFINITY, kVoteNone) is "nothing" and loses to every pixel.
+__device__ __forceinline__ bool vote_before(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+
 __device__ __forceinline__ void vote_argmax_first(float& v, int& idx) {
     // wave-wide (max value, then min index)
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) {
         const float v2 = __shfl_xor(v, m);
         const int i2 = __shfl_xor(idx, m);
-        if (v2 > v || (v2 == v && i2 < idx)) { v = v2; idx = i2; }
+        if (vote_before(v2, i2, v, idx)) { v = v2; idx = i2; }
     }
 }
 
-// One body for both entry kernels.  REPORT = false is vote_kernel: `rep` is never touched and every report store / load below
-// is compiled out (if constexpr), so the plain kernel keeps its instructions and its bits.
-template <bool REPORT>
-__device__ __forceinline__ void vote_body(const VoteParams& p, const VoteReport& rep) {
+// Refined heat of joint j at pixel m = b*npix + px: ((hm + 1) * hm3) * [tiny >= -0.99]
+__device__ __forceinline__ float vote_refined(const VoteParams& p, long m, float fg, int j) {
 #pragma clang fp contract(off)
-    DR_DYN_SMEM(smem_raw);
-    float* ref = reinterpret_cast<float*>(smem_raw);      // [kVoteJC][npix]
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int b = blockIdx.x;
-    const int j0 = blockIdx.y * kVoteJC;
-    const int npix = p.h * p.w;
-    const int J = p.J;
+    float r = (p.hm.p[m * p.hm.cs + p.hm.coff + j] + 1.0f) * p.hm3.p[m * p.hm3.cs + p.hm3.coff + j];
+    r = r * fg;
+    return r;
+}
+__device__ __forceinline__ float vote_foreground(const VoteParams& p, long m) { return (p.tiny[m] < kBackground) ? 0.0f : 1.0f; }
 
-    // ---- phase 1: refined heat-map of joints j0..j0+3 into LDS ---------------------------------
-    for (int px = tid; px < npix; px += 256) {
-        const long m = (long)b * npix + px;
-        const float fg = (p.tiny[m] < kBackground) ? 0.0f : 1.0f;
-        const float* hm = p.hm.p + m * p.hm.cs + p.hm.coff;
-        const float* h3 = p.hm3.p + m * p.hm3.cs + p.hm3.coff;
+// Phase 1 of both paths, all 256 threads: the refined heat of joints j0..j0+3 (-INFINITY for joints >= J) at pixels px0..px0+n-1 of
+// crop b into LDS, ref[jj * n + i].  Coalesced: consecutive threads read consecutive pixels, every thread the J channels of its pixel.
+__device__ __forceinline__ void vote_refine_to_lds(const VoteParams& p, int b, int j0, int px0, int n, float* ref) {
+    const int npix = p.h * p.w;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const long m = (long)b * npix + px0 + i;
+        const float fg = vote_foreground(p, m);
 #pragma unroll
         for (int jj = 0; jj < kVoteJC; ++jj) {
             const int j = j0 + jj;
-            float r = -INFINITY;
-            if (j < J) {
-                r = (hm[j] + 1.0f) * h3[j];
-                r = r * fg;
-            }
-            ref[jj * npix + px] = r;
+            ref[jj * n + i] = j < p.J ? vote_refined(p, m, fg, j) : -INFINITY;
         }
     }
-    __syncthreads();
+}
 
-    const int j = j0 + wave;
-    if (j >= J) return;            // whole wave leaves together
-    const float* rj = ref + wave * npix;
-
-    // ---- top-5 (tf.nn.top_k sorted, ties -> lower index) ---------------------------------------
-    int sel[5];
-    unsigned long long taken = 0ull;           // bit i: my i-th pixel (lane + 64*i) already selected
-    const int per_lane = (npix + 63) / 64;     // <= 64
+// Top-5 of one wave's n <= 4096 values in LDS (tf.nn.top_k sorted, ties -> lower index): five rounds of per-lane scan, wave-wide
+// arg-max and removal.  sel[k] = px0 + position and selv[k] = the value there (the winner's own bits); a round that finds nothing
+// selectable (only NaN left) gives (-INFINITY, kVoteNone), and so does every round after it.
+__device__ __forceinline__ void vote_top5(const float* rj, int n, int px0, int lane, float selv[5], int sel[5]) {
+    unsigned long long taken = 0ull;           // bit i: my i-th value (lane + 64*i) already selected
+    const int per_lane = (n + 63) / 64;        // <= 64
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
         float bv = -INFINITY;
-        int bi = 0x7fffffff;
+        int bi = kVoteNone;
         for (int i = 0; i < per_lane; ++i) {
             const int px = lane + 64 * i;
-            if (px < npix && !((taken >> i) & 1ull)) {
+            if (px < n && !((taken >> i) & 1ull)) {
                 const float v = rj[px];
-                if (v > bv || (v == bv && px < bi)) { bv = v; bi = px; }
+                if (vote_before(v, px, bv, bi)) { bv = v; bi = px; }
             }
         }
-        if (bi == 0x7fffffff) bv = -INFINITY;
         vote_argmax_first(bv, bi);
-        if (bi == 0x7fffffff) bi = 0;          // degenerate (all NaN): fall back to pixel 0
-        if ((bi & 63) == lane) taken |= 1ull << (bi >> 6);
-        sel[k] = bi;
+        if (bi != kVoteNone && (bi & 63) == lane) taken |= 1ull << (bi >> 6);
+        selv[k] = bv;
+        sel[k] = bi != kVoteNone ? px0 + bi : kVoteNone;
     }
+}
+
+// Everything behind the selection, for one wave = one (crop b, joint j): the report's heat-map peak, candidates + weights, start
+// cell, mean-shift, stores.  sel[] = the five pixels in top_k order, selv[] = the refined heat there (report only).  Shared by the
+// single-launch kernels (vote_body) and the tiled path's vote_finish_kernel.  REPORT = false: `rep` and `selv` are never touched and
+// every report store / load below is compiled out (if constexpr), so the plain kernels keep their instructions and their bits.
+template <bool REPORT>
+__device__ __forceinline__ void vote_tail(const VoteParams& p, const VoteReport& rep, int b, int j, int lane, const int sel[5],
+                                          const float selv[5]) {
+#pragma clang fp contract(off)
+    const int npix = p.h * p.w;
+    const int J = p.J;
 
     // ---- report: heat-map-only estimate, the first maximum of the RAW hm[b,:,:,j] (no depth mask) ---------------
     // Wave-local and lane-strided over the joint's column of hm, which phase 1 has just pulled through L2.  Ties -> lowest
@@ -159,14 +176,13 @@ __device__ __forceinline__ void vote_body(const VoteParams& p, const VoteReport&
         if (rep.hm_peak) {
             const float* hj = p.hm.p + (long)b * npix * p.hm.cs + p.hm.coff + j;
             float bv = -INFINITY;
-            int bi = 0x7fffffff;
+            int bi = kVoteNone;
             for (int px = lane; px < npix; px += 64) {
                 const float v = hj[(long)px * p.hm.cs];
-                if (v > bv || (v == bv && px < bi)) { bv = v; bi = px; }
+                if (vote_before(v, px, bv, bi)) { bv = v; bi = px; }
             }
-            if (bi == 0x7fffffff) bv = -INFINITY;
             vote_argmax_first(bv, bi);
-            if (bi == 0x7fffffff) bi = 0;
+            if (bi == kVoteNone) bi = 0;
             if (lane < 3) {
                 const float val = hj[(long)bi * p.hm.cs];
                 rep.hm_peak[((long)b * J + j) * 3 + lane] = lane == 0 ? (float)(bi % p.w) : (lane == 1 ? (float)(bi / p.w) : val);
@@ -182,8 +198,12 @@ __device__ __forceinline__ void vote_body(const VoteParams& p, const VoteReport&
     {
         const int me = lane < 5 ? lane : 0;
         int px = sel[0];
+        float score = selv[0];
 #pragma unroll
-        for (int k = 1; k < 5; ++k) px = (me == k) ? sel[k] : px;
+        for (int k = 1; k < 5; ++k) {
+            px = (me == k) ? sel[k] : px;
+            if constexpr (REPORT) score = (me == k) ? selv[k] : score;
+        }
         const long m = (long)b * npix + px;
         const CloudPoint cloud = cloud_point(cam, p.com + b * 3, p.tiny[m], px, p.w);
         // resume_om: um * (0.8 - hm3*0.8)
@@ -207,7 +227,7 @@ __device__ __forceinline__ void vote_body(const VoteParams& p, const VoteReport&
             if (lane < 5) {
                 const long o = ((long)b * J + j) * 5 + lane;
                 if (rep.can_idx) rep.can_idx[o] = px;
-                if (rep.can_score) rep.can_score[o] = rj[px];
+                if (rep.can_score) rep.can_score[o] = score;
                 if (rep.can_weight) rep.can_weight[o] = wt;
                 if (rep.can_pts) { rep.can_pts[3 * o + 0] = c0; rep.can_pts[3 * o + 1] = c1; rep.can_pts[3 * o + 2] = c2; }
                 if (rep.ori_pts) { rep.ori_pts[3 * o + 0] = cloud.X; rep.ori_pts[3 * o + 1] = cloud.Y; rep.ori_pts[3 * o + 2] = cloud.Z; }
@@ -298,6 +318,35 @@ __device__ __forceinline__ void vote_body(const VoteParams& p, const VoteReport&
     }
 }
 
+// Single launch, maps up to kVoteMaxPix: one body for both entry kernels (REPORT = false is vote_kernel).
+template <bool REPORT>
+__device__ __forceinline__ void vote_body(const VoteParams& p, const VoteReport& rep) {
+    DR_DYN_SMEM(smem_raw);
+    float* ref = reinterpret_cast<float*>(smem_raw);      // [kVoteJC][npix]
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int b = blockIdx.x;
+    const int j0 = blockIdx.y * kVoteJC;
+    const int npix = p.h * p.w;
+
+    // ---- phase 1: refined heat-map of joints j0..j0+3 into LDS ---------------------------------
+    vote_refine_to_lds(p, b, j0, 0, npix, ref);
+    __syncthreads();
+
+    const int j = j0 + wave;
+    if (j >= p.J) return;          // whole wave leaves together
+    const float* rj = ref + wave * npix;
+
+    // ---- top-5; degenerate (all NaN): fall back to pixel 0 --------------------------------------
+    int sel[5];
+    float selv[5];
+    vote_top5(rj, npix, 0, lane, selv, sel);
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+        if (sel[k] == kVoteNone) { sel[k] = 0; selv[k] = rj[0]; }
+    vote_tail<REPORT>(p, rep, b, j, lane, sel, selv);
+}
+
 __global__ __launch_bounds__(256) void vote_kernel(const VoteParams p) {
     vote_body<false>(p, VoteReport{});
 }
@@ -305,6 +354,88 @@ __global__ __launch_bounds__(256) void vote_kernel(const VoteParams p) {
 // The same vote plus the report: same launch geometry, same LDS plan, same xyz_mm bits.
 __global__ __launch_bounds__(256) void vote_report_kernel(const VoteParams p, const VoteReport rep) {
     vote_body<true>(p, rep);
+}
+
+// ---- tiled path: maps above kVoteMaxPix (the 128x128 maps of in_hw = 512), T = npix / kVoteTile tiles, two launches --------------
+// The LDS plan above and the 64-bit `taken` mask end at 4096 pixels, so the larger map is cut into tiles that run as workgroups of
+// their own.  The five largest of the map are among the five largest of their tiles and the order is total (pixel indices are
+// unique), so the merged selection is the single-launch selection: same pixels, same order, same bits downstream.  Traffic: the
+// single launch's (5J+1)*npix*4 B per crop plus 40*J*T B of workspace written and read back.
+//
+// DR_VOTE_NO_PK: the two kernels are compiled with the packed-fp32-ops target feature off, the rule for device code that is new
+// here (left alone, the compiler pairs the tail's fp32 operations into 108 v_pk_add_f32 / v_pk_mul_f32 in the finish kernel).
+// Device pass only; `flatten` keeps the HIP header functions inlining across the feature difference.  Same bits, scratch,
+// occupancy and time either way, 36 registers instead of 44.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define DR_VOTE_NO_PK __attribute__((flatten, target("no-packed-fp32-ops")))
+#else
+#define DR_VOTE_NO_PK
+#endif
+
+// Grid (tile, joint quad, crop), 256 threads, 64 KiB LDS: phase 1 over the tile's pixels (a workgroup still reads all J channels of
+// each of its pixels: the same coalesced pattern), then each wave stores its joint's top 5 of the tile to ws[b][j][tile][0..4].
+__global__ DR_VOTE_NO_PK __launch_bounds__(256) void vote_scan_kernel(const VoteParams p, VoteCand* ws) {
+    DR_DYN_SMEM(smem_raw);
+    float* ref = reinterpret_cast<float*>(smem_raw);      // [kVoteJC][kVoteTile]
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int tile = blockIdx.x, T = gridDim.x;
+    const int j0 = blockIdx.y * kVoteJC;
+    const int b = blockIdx.z;
+
+    vote_refine_to_lds(p, b, j0, tile * kVoteTile, kVoteTile, ref);
+    __syncthreads();
+
+    const int j = j0 + wave;
+    if (j >= p.J) return;          // whole wave leaves together
+    int sel[5];
+    float selv[5];
+    vote_top5(ref + wave * kVoteTile, kVoteTile, tile * kVoteTile, lane, selv, sel);
+
+    // lane k < 5 stores pair k
+    VoteCand c{selv[0], sel[0]};
+#pragma unroll
+    for (int k = 1; k < 5; ++k)
+        if (lane == k) c = VoteCand{selv[k], sel[k]};
+    if (lane < 5) ws[(((long)b * p.J + j) * T + tile) * 5 + lane] = c;
+}
+
+// Grid (crop, joint quad), one wave per joint, no LDS: lane l < 5T holds partial candidate l, five rounds of wave-wide arg-max with
+// removal merge them under vote_before, and vote_tail does the rest.  REPORT = false carries no report stores.
+template <bool REPORT>
+__global__ DR_VOTE_NO_PK __launch_bounds__(256) void vote_finish_kernel(const VoteParams p, const VoteReport rep, const VoteCand* ws, int T) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x;
+    const int j = blockIdx.y * kVoteJC + (threadIdx.x >> 6);
+    if (j >= p.J) return;          // whole wave leaves together
+
+    float cv = -INFINITY;
+    int ci = kVoteNone;
+    if (lane < 5 * T) {
+        const VoteCand c = ws[((long)b * p.J + j) * T * 5 + lane];
+        if (c.px != kVoteNone) { cv = c.v; ci = c.px; }
+    }
+
+    // ---- top-5 of the union; nothing left (all NaN): fall back to pixel 0 ----------------------
+    int sel[5];
+    float selv[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        float bv = cv;
+        int bi = ci;
+        vote_argmax_first(bv, bi);
+        if (bi != kVoteNone && bi == ci) { cv = -INFINITY; ci = kVoteNone; }
+        sel[k] = bi;
+        selv[k] = bv;
+        if (bi == kVoteNone) {
+            sel[k] = 0;
+            if constexpr (REPORT) {
+                const long m = (long)b * p.h * p.w;
+                selv[k] = vote_refined(p, m, vote_foreground(p, m), j);
+            }
+        }
+    }
+    vote_tail<REPORT>(p, rep, b, j, lane, sel, selv);
 }
 
 }  // namespace dr

@@ -117,7 +117,10 @@ int dr_forward_eval(dr_handle* h, int B, const float* dm_norm_dev, float* hm_dev
 int dr_read_maps(dr_handle* h, int B, int stack, float* hm_dev, float* hm3_dev, float* um_dev,
                  dr_stream stream);
 /* _resume_om + _xyz_estimation + unnorm_xyz_pose on caller-provided maps.
- * dm_norm (B,hw,hw,1), cfg (B,6)=fx,fy,cx,cy,w,h, com (B,3) -> xyz_mm (B,3J). */
+ * dm_norm (B,hw,hw,1), cfg (B,6)=fx,fy,cx,cy,w,h, com (B,3) -> xyz_mm (B,3J).
+ * Every in_hw dr_create accepts is voted: maps up to 4096 pixels (in_hw 128, 256) in one launch, the 128x128 maps of
+ * in_hw = 512 as two (a top-5 per tile of 4096 pixels, then the merge; the same pixels, order and bits as one launch
+ * would give).  The tiled path's workspace belongs to the handle and is allocated by dr_create. */
 int dr_vote(dr_handle* h, int B, const float* hm_dev, const float* hm3_dev, const float* um_dev,
             const float* dm_norm_dev, const float* cfg_dev, const float* com_dev, float* xyz_mm_dev,
             dr_stream stream);
@@ -151,8 +154,8 @@ struct dr_vote_report {
                              *           :808-811); NaN is never selected, nothing selected -> pixel 0.  self.hm_uvd_pts (:471) is
                              *           (u*in_hw/map_hw, v*in_hw/map_hw, 1) */
 };
-/* dr_vote plus the report, one launch of vote_report_kernel: same contract, same xyz_mm bits.  report must not be NULL
- * (DR_E_INVALID); maps above 4096 pixels are DR_E_UNSUPPORTED as in dr_vote. */
+/* dr_vote plus the report, written by the vote's own launches (vote_report_kernel; above 4096 pixels the tiled path's
+ * finish launch): same contract, same xyz_mm bits.  report must not be NULL (DR_E_INVALID). */
 int dr_vote_report(dr_handle* h, int B, const float* hm_dev, const float* hm3_dev, const float* um_dev,
                    const float* dm_norm_dev, const float* cfg_dev, const float* com_dev, float* xyz_mm_dev,
                    const struct dr_vote_report* report, dr_stream stream);

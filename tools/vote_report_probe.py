@@ -43,7 +43,7 @@ def maps(B, m, J, in_hw, dev, seed=11):
 
 def vote_ms(eng):
     rows = [r for r in eng.h.profile_read() if r['name'] == 'vote']
-    assert len(rows) == 1 and rows[0]['launches'] == 1, rows
+    assert len(rows) == 1 and rows[0]['launches'] in (1, 2), rows      # 2: scan + finish of the tiled vote (in_hw = 512)
     return rows[0]['total_ms']
 
 
