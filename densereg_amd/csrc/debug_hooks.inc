@@ -666,13 +666,14 @@ extern "C" int dr_dbg_bn_finalize_rows(int rows) {
 extern "C" int dr_dbg_force_x3(int mode) {
     if (mode < -1 || mode > 7) return DR_E_INVALID;         // (as 2 with: 3 one accumulator, 4 the three-stage LDS ring, 5 four waves per workgroup,
                                                             //  6 the debug entries store the input as P3 and conv_p3.h runs where its tile applies,
-                                                            //  7 conv_x3_kernel also where conv_x3h.h (the LDS-resident 3x3 halo) would run)
+                                                            //  7 conv_x3_kernel also where conv_x3h.h / conv_x3hw.h (the LDS-resident 3x3 halo) would run)
     g_dbg_x3 = mode;
     return DR_OK;
 }
 
 extern "C" long dr_dbg_p3_launches(void) { return g_p3_launches; }
 extern "C" long dr_dbg_x3h_launches(void) { return g_x3h_launches; }
+extern "C" long dr_dbg_x3hw_launches(void) { return g_x3hw_launches; }
 
 extern "C" int dr_dbg_force_bf16_storage(int on) {
     g_dbg_bf16_storage = on ? 1 : 0;

@@ -11,6 +11,7 @@
 #include "conv_x3.h"
 #include "conv_p3.h"
 #include "conv_x3h.h"
+#include "conv_x3hw.h"
 #include "conv_wgrad.h"
 #include "conv_wgrad_bf16.h"
 #include "conv_wgrad_tr.h"
@@ -88,6 +89,7 @@ static bool conv_use_glds(const ConvParams& p) {
 }
 
 static long g_x3h_launches = 0;      // conv_x3h.h launches of this process (dr_dbg_x3h_launches)
+static long g_x3hw_launches = 0;     // conv_x3hw.h launches of this process (dr_dbg_x3hw_launches)
 static long g_p3_launches = 0;       // conv_p3.h launches of this process (test hook dr_dbg_p3_launches: "the kernel under test is the one that ran")
 static int g_force_tile = -1;        // test/bench hook (dr_dbg_conv_bench); -1 = heuristic
 static int g_dbg_bf16 = 0;           // test/bench hook (dr_dbg_force_bf16): dr_dbg_conv2d / dr_dbg_conv_bench run the bf16 kernels
@@ -170,6 +172,18 @@ static int g_dbg_x3 = -1;            // test/bench hook (dr_dbg_force_x3): overr
 static bool conv_x3h_shape(const ConvParams& p) {
     static const bool halo_on = [] { const char* e = getenv("DR_X3_HALO"); return !(e && e[0] == '0'); }();
     return halo_on && g_dbg_x3 != 7 && p.ksize == 3 && !p.rowmask && (p.W == 32 || p.W == 16) && (p.H * p.W) % 128 == 0;
+}
+// conv_x3hw.h: the halo kernel on 256-row blocks for the 64- and 128-pixel-wide maps (256x256 / 512x512 crops), in place of conv_x3_kernel
+// where the x3 family is selected already -- every width and tile it has, under the default rule too: each measured faster than
+// conv_x3_kernel beyond the spread between repeats, down to the smallest grids conv_use_x3 admits (profiles/x3h_wide.md: 1.04-1.40x).
+// DR_X3_HALO=0 / dr_dbg_force_x3(7) turn it off with conv_x3h.h, DR_X3_HALOW=0 alone.
+static bool conv_x3hw_shape(const ConvParams& p) {
+    static const bool on = [] {
+        const char* e = getenv("DR_X3_HALO"); const char* w = getenv("DR_X3_HALOW");
+        return !(e && e[0] == '0') && !(w && w[0] == '0');
+    }();
+    return on && g_dbg_x3 != 7 && p.ksize == 3 && !p.rowmask && (p.W == 64 || p.W == 128) && (p.H * p.W) % 256 == 0 &&
+           (p.grp_rows <= 0 || p.grp_rows % 256 == 0);
 }
 // conv_x3_kernel's weight tiles by a hidden LDS-DMA (conv_x3.h, BD); DR_X3_BD=0: through registers
 static bool x3_bd() {
@@ -313,6 +327,22 @@ int launch_conv_igemm(const ConvParams& p, hipStream_t s) {
         const bool w4 = (variant & 4) || g_dbg_x3 == 5 || one_acc || ring;
         if (bn160) {                                                         // (no halo form, no variants)
             DR_LAUNCH((conv_x3_kernel<128, 160, 1, 0, 4, 4, 1>), grid, dim3(256), 0, s, q);
+            return 0;
+        }
+        if (conv_x3hw_shape(p) && !one_acc && !ring && !w4) {        // (256-row blocks: its own grid; statistics rows stay 128 pixel rows)
+            const dim3 gw((unsigned)(M / 256), bn96 ? 1 : dr_ceil_div(ncols, bn64 ? 64 : 128));
+            q.gx = (int)gw.x; q.gy = (int)gw.y;
+            if (bn96) {
+                if (p.W == 64) DR_LAUNCH((conv_x3hw_kernel<96, 64, 256, 8, 8>), gw, dim3(512), 0, s, q);
+                else DR_LAUNCH((conv_x3hw_kernel<96, 128, 256, 8, 8>), gw, dim3(512), 0, s, q);
+            } else if (bn64) {
+                if (p.W == 64) DR_LAUNCH((conv_x3hw_kernel<64, 64, 256, 8, 4>), gw, dim3(512), 0, s, q);
+                else DR_LAUNCH((conv_x3hw_kernel<64, 128, 256, 8, 4>), gw, dim3(512), 0, s, q);
+            } else {
+                if (p.W == 64) DR_LAUNCH((conv_x3hw_kernel<128, 64>), gw, dim3(1024), 0, s, q);
+                else DR_LAUNCH((conv_x3hw_kernel<128, 128>), gw, dim3(1024), 0, s, q);
+            }
+            ++g_x3hw_launches;
             return 0;
         }
         if (conv_x3h_shape(p) && !one_acc && !ring && !w4) {

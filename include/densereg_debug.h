@@ -129,6 +129,9 @@ long dr_dbg_p3_launches(void);
 /* ... 7: as 2, but conv_x3_kernel also where conv_x3h_kernel (densereg_amd/csrc/conv_x3h.h: 3x3 layers with the haloed input tile resident in
  * LDS across the nine taps) would run.  dr_dbg_x3h_launches: conv_x3h_kernel launches of this process so far. */
 long dr_dbg_x3h_launches(void);
+/* dr_dbg_x3hw_launches: conv_x3hw_kernel launches (densereg_amd/csrc/conv_x3hw.h: the halo kernel on 256-row blocks for 64- and 128-pixel-wide
+ * images) of this process so far; mode 7 and DR_X3_HALO=0 turn that kernel off too, DR_X3_HALOW=0 that kernel alone. */
+long dr_dbg_x3hw_launches(void);
 
 /* Partial statistics rows one wave of a BatchReNorm finalize launch folds before the micro-batch group gets another wave
  * (densereg_amd/csrc/train_kernels.h: bn_finalize_split; default 512, 0 restores it).  Process-global; tests lower it so that

@@ -4,6 +4,7 @@ hipcc's -Rpass-analysis=kernel-resource-usage for gfx950 (no GPU needed).
 
     python tools/kernel_resources.py > profiles/r01_kernel_resources.md
 """
+import functools
 import os
 import re
 import subprocess
@@ -12,6 +13,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+@functools.lru_cache(maxsize=None)            # (one product build per process, whoever asks)
 def collect():
     """[(demangled kernel name, {'vgpr', 'agpr', 'sgpr', 'scratch', 'lds', 'occ'})] of the product build.  Compiles the product's
     sources with the resource remarks INTO A TEMPORARY DIRECTORY: the shipped densereg_amd/lib/*.so is never touched."""
