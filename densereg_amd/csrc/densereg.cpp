@@ -17,6 +17,7 @@
 #include "conv_wgrad_tr.h"
 #include "conv_wgrad_x3.h"
 #include "frontend.h"
+#include "hg_fused_bf16.h"
 #include "dataio.h"
 #include "kernels_misc.h"
 #include "net.h"
@@ -1261,11 +1262,13 @@ int dr_set_precision(dr_handle* h, int precision) {
 
 int dr_set_fusion(dr_handle* h, int on) {
     if (!h) return DR_E_INVALID;
-    if ((on != 0) != h->fuse_tail) {
+    const bool tail = on != DR_FUSION_OFF, all = on == DR_FUSION_ALL;
+    if (tail != h->fuse_tail || all != h->fuse_bf16) {
         for (auto& g : h->graphs) rt::graph_destroy(g.g);                       // recorded launches name the other set of kernels
         h->graphs.clear();
     }
-    h->fuse_tail = on != 0;
+    h->fuse_tail = tail;
+    h->fuse_bf16 = all;
     return DR_OK;
 }
 
@@ -1502,8 +1505,46 @@ static int run_simple_op(dr_handle* h, const Op& op, int B, hipStream_t s, bool 
     return DR_OK;
 }
 
+// ... under DR_PREC_BF16 (hg_fused_bf16.h): the weights are the bf16 pack [Kp/32][tap][Np][32] the unfused bf16 convolutions read.
+// Eight waves per workgroup from F = 128 (the column tiles over two waves per SIMD): measured against four, the launch takes
+// 40.6 against 43.9 us at F = 128 and 94 against 114 us at F = 256 (profiles/hg_fused_bf16.md); F = 64 has tiles for four.
+static int run_fused_region_bf16(dr_handle* h, const FusedRegion& fr, int B, hipStream_t s) {
+    HgFusedParams16 p{};
+    p.x = fr.in.t->p; p.x_cs = fr.in.t->cs; p.x_coff = fr.in.coff;
+    p.y = fr.out.t->p; p.y_cs = fr.out.t->cs; p.y_coff = fr.out.coff;
+    p.B = B; p.F = fr.in.C;
+    double flops = 0;
+    for (int i = 0; i < 24; ++i) {
+        const ConvLayer& c = h->convs[fr.conv[i]];
+        p.conv[i].w = reinterpret_cast<const __bf16*>(h->wp + c.wp_off); p.conv[i].Np = c.Np;
+        p.conv[i].scale = h->fold + c.fold_off; p.conv[i].shift = h->fold + c.fold_off + c.cout;
+        flops += 2.0 * B * c.H * c.W * c.k * c.k * c.cin * c.cout;
+    }
+    const void* fn = p.F == 64 ? (const void*)hg_tail_eval_bf16_kernel<64, 4> : p.F == 128 ? (const void*)hg_tail_eval_bf16_kernel<128, 8>
+                   : p.F == 192 ? (const void*)hg_tail_eval_bf16_kernel<192, 8> : (const void*)hg_tail_eval_bf16_kernel<256, 8>;
+    const size_t lds = (size_t)hg_fused_bf16_lds_bytes(p.F);
+    if (lds > 64 * 1024) {                                      // asked once per (device, instance), as for the fp32 kernel
+        static std::mutex mu;
+        static std::map<std::pair<int, int>, bool> granted;
+        std::lock_guard<std::mutex> lk(mu);
+        const auto key = std::make_pair(h->cfg.device, p.F);
+        auto it = granted.find(key);
+        if (it == granted.end()) it = granted.emplace(key, rt::allow_dyn_lds(fn, lds)).first;
+        if (!it->second) return DR_E_UNSUPPORTED;              // (the caller falls back to the unfused ops)
+    }
+    ProfScope ps(h, s, KID_HG_FUSED, flops, 4.0 * B * p.F * (256.0 + 64.0));
+    switch (p.F) {                                              // (hg_fused_bf16_supported: multiples of 64 up to 256)
+        case 64: DR_LAUNCH((hg_tail_eval_bf16_kernel<64, 4>), dim3(B), dim3(256), lds, s, p); break;
+        case 128: DR_LAUNCH((hg_tail_eval_bf16_kernel<128, 8>), dim3(B), dim3(512), lds, s, p); break;
+        case 192: DR_LAUNCH((hg_tail_eval_bf16_kernel<192, 8>), dim3(B), dim3(512), lds, s, p); break;
+        default: DR_LAUNCH((hg_tail_eval_bf16_kernel<256, 8>), dim3(B), dim3(512), lds, s, p); break;
+    }
+    return DR_OK;
+}
+
 // the bottom of an hourglass as one launch (hg_fused.h)
 static int run_fused_region(dr_handle* h, const FusedRegion& fr, int B, hipStream_t s) {
+    if (h->precision == 1) return run_fused_region_bf16(h, fr, B, s);
     HgFusedParams p{};
     p.x = fr.in.t->p; p.x_cs = fr.in.t->cs; p.x_coff = fr.in.coff;
     p.y = fr.out.t->p; p.y_cs = fr.out.t->cs; p.y_coff = fr.out.coff;
@@ -1542,8 +1583,9 @@ static int run_fused_region(dr_handle* h, const FusedRegion& fr, int B, hipStrea
 }
 
 static bool fused_tail_usable(const dr_handle* h) {
-    return h->fuse_tail && !h->fused.empty() && !h->multi_stream && h->precision == 0 && hg_fused_supported(h->cfg.num_fea) &&
-           h->cfg.kernel_size == 3;
+    if (!h->fuse_tail || h->fused.empty() || h->multi_stream || h->cfg.kernel_size != 3) return false;
+    if (h->precision == 0) return hg_fused_supported(h->cfg.num_fea);
+    return h->fuse_bf16 && hg_fused_bf16_supported(h->cfg.num_fea);         // DR_FUSION_ALL: hg_fused_bf16.h
 }
 
 static int forward_eval_impl(dr_handle* h, int B, const float* dm, hipStream_t s) {

@@ -201,10 +201,11 @@ class Engine:
         the handle and the packed weights follow the precision)."""
         self.h.call('dr_set_precision', {'f32': 0, 'bf16': 1}[precision])
 
-    def set_fusion(self, on: bool):
-        """Eval mode: the part of every hourglass below 16x16 pixels as one launch (``dr_set_fusion``; on by default).  Off keeps
-        every layer's output in HBM (``read_activation``)."""
-        self.h.call('dr_set_fusion', 1 if on else 0)
+    def set_fusion(self, on: bool, bf16: bool = False):
+        """Eval mode: the part of every hourglass below 16x16 pixels as one launch (``dr_set_fusion``; on by default for 'f32').
+        ``bf16=True`` also takes the launch under ``set_precision('bf16')`` (``DR_FUSION_ALL``; opt-in: the region's inner layers
+        then live only in LDS).  Off keeps every layer's output in HBM (``read_activation``)."""
+        self.h.call('dr_set_fusion', (2 if bf16 else 1) if on else 0)
 
     def load_params(self, params: Dict[str, np.ndarray]):
         self.h.load_params(params)

@@ -63,6 +63,10 @@ class ReplicaPool:
         for e in self.engines:
             e.set_precision(precision)
 
+    def set_fusion(self, on: bool, bf16: bool = False):
+        for e in self.engines:
+            e.set_fusion(on, bf16=bf16)
+
     def load_params(self, params: Dict[str, np.ndarray]):
         for e in self.engines:
             e.load_params(params)

@@ -347,10 +347,19 @@ int dr_depth_from_samples(const uint8_t* samples_dev, long npix, int mode, float
 int dr_set_precision(dr_handle* h, int precision);
 
 /* ---- eval-mode fusion ---------------------------------------------------------------------------- */
-/* In eval mode (dr_forward_eval / dr_infer, fp32 matrix cores, num_fea a multiple of 32 up to 128) the part of every hourglass
- * below 16x16 pixels -- 24 convolutions, 3 pools, 2 upsample-adds of network/um_v1.py:51-69 -- runs as ONE launch with its
- * intermediate tensors in LDS (on by default; same results up to fp32 summation order).  on = 0 launches every op on its own, which
- * also keeps every layer's output in HBM for dr_read_activation. */
+/* In eval mode (dr_forward_eval / dr_infer / dr_infer_report) the part of every hourglass below 16x16 pixels -- 24 convolutions,
+ * 3 pools, 2 upsample-adds of network/um_v1.py:51-69 -- can run as ONE launch with its intermediate tensors in LDS:
+ *   DR_FUSION_OFF  every op is a launch of its own, and every layer's output stays in HBM for dr_read_activation;
+ *   DR_FUSION_F32  (default) one launch on a DR_PREC_F32 handle with num_fea a multiple of 32 up to 128 (same results up to fp32
+ *                  summation order); a DR_PREC_BF16 handle launches every op on its own;
+ *   DR_FUSION_ALL  ... and one launch on a DR_PREC_BF16 handle with num_fea a multiple of 64 up to 256 (bf16 operands, fp32
+ *                  accumulation, fp32 epilogues and skip adds: the arithmetic of the unfused bf16 path up to summation order).  Opt-in
+ *                  because a fused region's inner layers live only in LDS: dr_read_activation fails on them.  On a DR_PREC_F32
+ *                  handle the same as DR_FUSION_F32.
+ * Where the launch does not apply (another num_fea, a device that refuses its LDS) the ops run one by one, silently. */
+#define DR_FUSION_OFF 0
+#define DR_FUSION_F32 1
+#define DR_FUSION_ALL 2
 int dr_set_fusion(dr_handle* h, int on);
 
 /* ---- introspection (tests / profiling) ----------------------------------------------------------- */
