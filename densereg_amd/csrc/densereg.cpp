@@ -18,6 +18,7 @@
 #include "conv_wgrad_x3.h"
 #include "frontend.h"
 #include "hg_fused_bf16.h"
+#include "hg_fused_x3.h"
 #include "dataio.h"
 #include "kernels_misc.h"
 #include "net.h"
@@ -1542,9 +1543,42 @@ static int run_fused_region_bf16(dr_handle* h, const FusedRegion& fr, int B, hip
     return DR_OK;
 }
 
+// ... on an fp32 handle with num_fea 192 or 256 under DR_FUSION_ALL (hg_fused_x3.h): fp32-accurate products from the three bf16 planes
+// of h->wp3, the ones the unfused x3 convolutions read.  Eight waves, a ring of six weight fragments (profiles/hg_fused_x3.md).
+static int run_fused_region_x3(dr_handle* h, const FusedRegion& fr, int B, hipStream_t s) {
+    HgFusedParamsX3 p{};
+    p.x = fr.in.t->p; p.x_cs = fr.in.t->cs; p.x_coff = fr.in.coff;
+    p.y = fr.out.t->p; p.y_cs = fr.out.t->cs; p.y_coff = fr.out.coff;
+    p.B = B; p.F = fr.in.C;
+    double flops = 0;
+    for (int i = 0; i < 24; ++i) {
+        const ConvLayer& c = h->convs[fr.conv[i]];
+        p.conv[i].w = h->wp3 + 3 * c.wp_off; p.conv[i].Np = c.Np;
+        p.conv[i].scale = h->fold + c.fold_off; p.conv[i].shift = h->fold + c.fold_off + c.cout;
+        flops += 2.0 * B * c.H * c.W * c.k * c.k * c.cin * c.cout;
+    }
+    constexpr int NW = DR_HGX3_WAVES;
+    const void* fn = p.F == 192 ? (const void*)hg_tail_eval_x3_kernel<192, NW> : (const void*)hg_tail_eval_x3_kernel<256, NW>;
+    const size_t lds = (size_t)hg_fused_x3_lds_bytes(p.F);
+    {                                                           // (always > 64 KB) asked once per (device, instance), as for the siblings
+        static std::mutex mu;
+        static std::map<std::pair<int, int>, bool> granted;
+        std::lock_guard<std::mutex> lk(mu);
+        const auto key = std::make_pair(h->cfg.device, p.F);
+        auto it = granted.find(key);
+        if (it == granted.end()) it = granted.emplace(key, rt::allow_dyn_lds(fn, lds)).first;
+        if (!it->second) return DR_E_UNSUPPORTED;              // (the caller falls back to the unfused ops)
+    }
+    ProfScope ps(h, s, KID_HG_FUSED, flops, 4.0 * B * p.F * (256.0 + 64.0));
+    if (p.F == 192) DR_LAUNCH((hg_tail_eval_x3_kernel<192, NW>), dim3(B), dim3(NW * 64), lds, s, p);
+    else DR_LAUNCH((hg_tail_eval_x3_kernel<256, NW>), dim3(B), dim3(NW * 64), lds, s, p);
+    return DR_OK;
+}
+
 // the bottom of an hourglass as one launch (hg_fused.h)
 static int run_fused_region(dr_handle* h, const FusedRegion& fr, int B, hipStream_t s) {
     if (h->precision == 1) return run_fused_region_bf16(h, fr, B, s);
+    if (!hg_fused_supported(fr.in.C)) return run_fused_region_x3(h, fr, B, s);      // (fused_tail_usable: num_fea 192, 256 under DR_FUSION_ALL)
     HgFusedParams p{};
     p.x = fr.in.t->p; p.x_cs = fr.in.t->cs; p.x_coff = fr.in.coff;
     p.y = fr.out.t->p; p.y_cs = fr.out.t->cs; p.y_coff = fr.out.coff;
@@ -1584,7 +1618,8 @@ static int run_fused_region(dr_handle* h, const FusedRegion& fr, int B, hipStrea
 
 static bool fused_tail_usable(const dr_handle* h) {
     if (!h->fuse_tail || h->fused.empty() || h->multi_stream || h->cfg.kernel_size != 3) return false;
-    if (h->precision == 0) return hg_fused_supported(h->cfg.num_fea);
+    if (h->precision == 0)                                                  // hg_fused.h, or DR_FUSION_ALL at 192 | 256: hg_fused_x3.h
+        return hg_fused_supported(h->cfg.num_fea) || (h->fuse_bf16 && h->wp3 && hg_fused_x3_supported(h->cfg.num_fea));
     return h->fuse_bf16 && hg_fused_bf16_supported(h->cfg.num_fea);         // DR_FUSION_ALL: hg_fused_bf16.h
 }
 

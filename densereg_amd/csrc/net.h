@@ -205,7 +205,7 @@ struct dr_handle {
     int precision = 0;                                      // dr_set_precision: 0 = fp32 MFMA, 1 = bf16 MFMA (inference handles)
     std::vector<dr::FusedRegion> fused;                     // one per stack (graph builder); used by the eval forward when fuse_tail
     bool fuse_tail = true;                                  // dr_set_fusion / DR_FUSE_TAIL=0: every op of the hourglass bottoms launches on its own
-    bool fuse_bf16 = false;                                 // dr_set_fusion(h, DR_FUSION_ALL): ... also under DR_PREC_BF16 (hg_fused_bf16.h)
+    bool fuse_bf16 = false;                                 // dr_set_fusion(h, DR_FUSION_ALL): ... also under DR_PREC_BF16 (hg_fused_bf16.h) and on fp32 at num_fea 192 | 256 (hg_fused_x3.h)
     bool last_eval_fused = false;                           // the last eval forward skipped the fused regions' intermediate tensors
     bool fuse_bn_bwd = true;                               // DR_FUSE_BN_BWD=0: every BatchReNorm layer runs its own reduce pass
     bool multi_stream = false;                             // DR_MULTI_STREAM=1 turns the lanes on; off or profiling: every lane = caller's stream

@@ -204,7 +204,8 @@ class Engine:
     def set_fusion(self, on: bool, bf16: bool = False):
         """Eval mode: the part of every hourglass below 16x16 pixels as one launch (``dr_set_fusion``; on by default for 'f32').
         ``bf16=True`` also takes the launch under ``set_precision('bf16')`` (``DR_FUSION_ALL``; opt-in: the region's inner layers
-        then live only in LDS).  Off keeps every layer's output in HBM (``read_activation``)."""
+        then live only in LDS), and under 'f32' with ``num_fea`` 192 or 256, where the default has no fused kernel (fp32-accurate
+        products from three bf16 planes per operand, ``hg_fused_x3.h``).  Off keeps every layer's output in HBM (``read_activation``)."""
         self.h.call('dr_set_fusion', (2 if bf16 else 1) if on else 0)
 
     def load_params(self, params: Dict[str, np.ndarray]):

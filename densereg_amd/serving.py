@@ -64,6 +64,8 @@ class ReplicaPool:
             e.set_precision(precision)
 
     def set_fusion(self, on: bool, bf16: bool = False):
+        """``Engine.set_fusion`` on every engine; ``bf16=True`` (``DR_FUSION_ALL``) also fuses the hourglass bottoms under 'bf16' and,
+        under 'f32', at ``num_fea`` 192 and 256."""
         for e in self.engines:
             e.set_fusion(on, bf16=bf16)
 

@@ -355,7 +355,8 @@ int dr_set_precision(dr_handle* h, int precision);
  *   DR_FUSION_ALL  ... and one launch on a DR_PREC_BF16 handle with num_fea a multiple of 64 up to 256 (bf16 operands, fp32
  *                  accumulation, fp32 epilogues and skip adds: the arithmetic of the unfused bf16 path up to summation order).  Opt-in
  *                  because a fused region's inner layers live only in LDS: dr_read_activation fails on them.  On a DR_PREC_F32
- *                  handle the same as DR_FUSION_F32.
+ *                  handle with num_fea up to 128 the same as DR_FUSION_F32; with num_fea 192 or 256 one launch with fp32-accurate
+ *                  products from three bf16 planes per operand (the arithmetic of the unfused path's x3 convolutions).
  * Where the launch does not apply (another num_fea, a device that refuses its LDS) the ops run one by one, silently. */
 #define DR_FUSION_OFF 0
 #define DR_FUSION_F32 1
