@@ -525,6 +525,7 @@ extern "C" int dr_dbg_conv_bench(int B, int H, int W, int Cin, int Cout, int k, 
     p.x = x; p.x_cs = x_cs; p.Cin = Cin; p.B = B; p.H = H; p.W = W; p.ksize = k;
     p.w = wp; p.Kp = Kp; p.Np = Np; p.y = y; p.y_cs = y_cs; p.Cout = Cout; p.scale = sc; p.shift = sc; p.relu = 1;
     if (bf) { p.bf16 = 1; p.Kp = dr_round_up(Cin, 32); }
+    if (bf && g_dbg_bf16_storage) p.x_bf16 = 1;             // (timing only: the first half of the fp32 buffer read as bf16 elements, same strides)
     __bf16* w3 = nullptr;
     if (!bf && g_dbg_x3 != 0 && (abl == 0 || abl == 6)) {            // (abl 6: the product kernel on all-zero operands)
         w3 = (__bf16*)rt::dmalloc((size_t)taps * Kp * Np * 3 * sizeof(__bf16));
@@ -674,6 +675,14 @@ extern "C" int dr_dbg_force_x3(int mode) {
 extern "C" long dr_dbg_p3_launches(void) { return g_p3_launches; }
 extern "C" long dr_dbg_x3h_launches(void) { return g_x3h_launches; }
 extern "C" long dr_dbg_x3hw_launches(void) { return g_x3hw_launches; }
+
+// conv_bf16h.h in the debug entries and in every handle of this process: -1 = DR_BF16_HALO / the measured rule, 0 = never, 1 = wherever it can run
+extern "C" int dr_dbg_force_bf16_halo(int on) {
+    if (on < -1 || on > 1) return DR_E_INVALID;
+    g_dbg_bf16h = on;
+    return DR_OK;
+}
+extern "C" long dr_dbg_bf16h_launches(void) { return g_bf16h_launches; }
 
 extern "C" int dr_dbg_force_bf16_storage(int on) {
     g_dbg_bf16_storage = on ? 1 : 0;

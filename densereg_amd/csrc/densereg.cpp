@@ -12,6 +12,7 @@
 #include "conv_p3.h"
 #include "conv_x3h.h"
 #include "conv_x3hw.h"
+#include "conv_bf16h.h"
 #include "conv_wgrad.h"
 #include "conv_wgrad_bf16.h"
 #include "conv_wgrad_tr.h"
@@ -92,6 +93,8 @@ static bool conv_use_glds(const ConvParams& p) {
 
 static long g_x3h_launches = 0;      // conv_x3h.h launches of this process (dr_dbg_x3h_launches)
 static long g_x3hw_launches = 0;     // conv_x3hw.h launches of this process (dr_dbg_x3hw_launches)
+static long g_bf16h_launches = 0;    // conv_bf16h.h launches of this process (dr_dbg_bf16h_launches)
+static int g_dbg_bf16h = -1;         // test/bench hook (dr_dbg_force_bf16_halo): -1 = DR_BF16_HALO / the measured rule, 0 = never, 1 = wherever the kernel can run
 static long g_p3_launches = 0;       // conv_p3.h launches of this process (test hook dr_dbg_p3_launches: "the kernel under test is the one that ran")
 static int g_force_tile = -1;        // test/bench hook (dr_dbg_conv_bench); -1 = heuristic
 static int g_dbg_bf16 = 0;           // test/bench hook (dr_dbg_force_bf16): dr_dbg_conv2d / dr_dbg_conv_bench run the bf16 kernels
@@ -239,6 +242,59 @@ bool conv_use_x3(const ConvParams& p) {
     if (ncols % 128 == 0) return dr_ceil_div((int)M, 128) * (long)(ncols / 128) >= min_wgs && (long)p.ksize * p.ksize * p.Kp >= 128;
     if (ncols == 96) return bn96 && dr_ceil_div((int)M, 128) >= 2 * min_wgs && (long)p.ksize * p.ksize * p.Kp >= 128;
     return bn64 && ncols % 64 == 0 && dr_ceil_div((int)M, 128) * (long)(ncols / 64) >= 2 * min_wgs && (long)p.ksize * p.ksize * p.Kp >= 128;
+}
+
+// conv_bf16h.h: the LDS-resident 3x3 halo kernel of the bf16 path, in place of conv_igemm's BF kernel on its 64-row tiles (64x128, 64x64, 64x96:
+// the arithmetic and the statistics rows the kernel reproduces bit for bit; the 128-row tiles of very deep grids and the split-K kernel of
+// grids that cannot fill the chip keep their launches).  Needs 128-row blocks of whole rows of a 16- or 32-pixel-wide image that lie in one
+// micro-batch group.  DR_BF16_HALO=0 / dr_dbg_force_bf16_halo(0): never; dr_dbg_force_bf16_halo(1): wherever it can run; otherwise the
+// measured rule (bf16h_grid_wired: every (W, column tile, storage) class, on grids of at least 160 workgroups).
+// Measured per launch against conv_igemm's BF kernel, alternating in one process (profiles/conv_bf16_halo.md): every (W, column tile, storage)
+// class is faster beyond the spread between repeats (1.03-1.72x) from 160 workgroups on; the one grid measured below that (16x16 64->64 at 40
+// crops: 80 four-wave workgroups on 256 CUs, where conv_igemm's 64x64 tile has 160) lost 7-10 % and stays on conv_igemm.
+static bool bf16h_grid_wired(long workgroups) { return workgroups >= 160; }
+static bool conv_use_bf16h(const ConvParams& p) {
+    static const bool env_on = [] { const char* e = getenv("DR_BF16_HALO"); return !(e && e[0] == '0'); }();
+    const int mode = g_dbg_bf16h >= 0 ? g_dbg_bf16h : (env_on ? -1 : 0);
+    if (mode == 0 || !p.bf16 || p.ksize != 3 || p.rowmask || (p.W != 16 && p.W != 32) || (p.H * p.W) % 128 != 0 || p.Kp % 32 != 0) return false;
+    if (p.grp_rows > 0 && p.grp_rows % 128 != 0) return false;
+    const int t = conv_tile_id(p), ncols = p.Ng > 0 ? p.Ng : p.Np;
+    if (t != KID_CONV_64x128 && t != KID_CONV_64x64 && !(t == KID_CONV_64x96 && ncols == 96)) return false;
+    if (mode == 1) return true;
+    const int bn = t == KID_CONV_64x128 ? 128 : t == KID_CONV_64x64 ? 64 : 96;
+    return bf16h_grid_wired((long)(p.B * p.H * p.W / 128) * dr_ceil_div(ncols, bn));
+}
+template <int BN, int NW, int WM>
+static void launch_bf16h_tile(const ConvParams& q, dim3 grid, hipStream_t s) {
+    const int xb = (q.x_bf16 ? 1 : 0) | ((q.y_bf16 || q.bst_raw_bf16) ? 2 : 0);
+    if (q.W == 32) {
+        switch (xb) {
+            case 0: DR_LAUNCH((conv_bf16h_kernel<BN, 5, NW, WM, 0>), grid, dim3(NW * 64), 0, s, q); break;
+            case 1: DR_LAUNCH((conv_bf16h_kernel<BN, 5, NW, WM, 1>), grid, dim3(NW * 64), 0, s, q); break;
+            case 2: DR_LAUNCH((conv_bf16h_kernel<BN, 5, NW, WM, 2>), grid, dim3(NW * 64), 0, s, q); break;
+            default: DR_LAUNCH((conv_bf16h_kernel<BN, 5, NW, WM, 3>), grid, dim3(NW * 64), 0, s, q); break;
+        }
+    } else {
+        switch (xb) {
+            case 0: DR_LAUNCH((conv_bf16h_kernel<BN, 4, NW, WM, 0>), grid, dim3(NW * 64), 0, s, q); break;
+            case 1: DR_LAUNCH((conv_bf16h_kernel<BN, 4, NW, WM, 1>), grid, dim3(NW * 64), 0, s, q); break;
+            case 2: DR_LAUNCH((conv_bf16h_kernel<BN, 4, NW, WM, 2>), grid, dim3(NW * 64), 0, s, q); break;
+            default: DR_LAUNCH((conv_bf16h_kernel<BN, 4, NW, WM, 3>), grid, dim3(NW * 64), 0, s, q); break;
+        }
+    }
+}
+static void launch_bf16h(const ConvParams& p, hipStream_t s) {
+    static const int nfast = [] { const char* e = getenv("DR_CONV_NFAST"); return (e && e[0] == '0') ? 0 : 1; }();
+    ConvParams q = p;
+    q.nfast = nfast;
+    const int t = conv_tile_id(p), ncols = p.Ng > 0 ? p.Ng : p.Np;
+    const int bn = t == KID_CONV_64x128 ? 128 : t == KID_CONV_64x64 ? 64 : 96;
+    const dim3 grid((unsigned)(p.B * p.H * p.W / 128), (unsigned)dr_ceil_div(ncols, bn));
+    q.gx = (int)grid.x; q.gy = (int)grid.y;
+    if (bn == 128) launch_bf16h_tile<128, 8, 2>(q, grid, s);
+    else if (bn == 64) launch_bf16h_tile<64, 4, 2>(q, grid, s);
+    else launch_bf16h_tile<96, 4, 4>(q, grid, s);
+    ++g_bf16h_launches;
 }
 
 // conv_p3.h (the x3 products on an input stored as its three bf16 planes): what the kernel can run -- whole 128-column blocks, at
@@ -413,6 +469,7 @@ int launch_conv_igemm(const ConvParams& p, hipStream_t s) {
     }
     if (p.bf16) {
         if (p.Kp % 32) return -1;
+        if (conv_use_bf16h(p)) { launch_bf16h(p, s); return 0; }
         switch (conv_tile_id(p)) {
             case KID_CONV_128x128: launch_cfg<128, 128, 2, 2, 16, 0, 1>(p, s); break;
             case KID_CONV_64x128: launch_cfg<64, 128, 2, 2, 16, 0, 1>(p, s); break;

@@ -132,6 +132,11 @@ long dr_dbg_x3h_launches(void);
 /* dr_dbg_x3hw_launches: conv_x3hw_kernel launches (densereg_amd/csrc/conv_x3hw.h: the halo kernel on 256-row blocks for 64- and 128-pixel-wide
  * images) of this process so far; mode 7 and DR_X3_HALO=0 turn that kernel off too, DR_X3_HALOW=0 that kernel alone. */
 long dr_dbg_x3hw_launches(void);
+/* conv_bf16h_kernel (densereg_amd/csrc/conv_bf16h.h: the 3x3 halo kernel of the bf16 path, in place of conv_igemm's BF kernel on its 64-row tiles):
+ * -1 = DR_BF16_HALO / the measured rule, 0 = never, 1 = wherever the kernel can run -- for the debug entries and every handle of the process.
+ * dr_dbg_bf16h_launches: its launches of this process so far. */
+int dr_dbg_force_bf16_halo(int on);
+long dr_dbg_bf16h_launches(void);
 
 /* Partial statistics rows one wave of a BatchReNorm finalize launch folds before the micro-batch group gets another wave
  * (densereg_amd/csrc/train_kernels.h: bn_finalize_split; default 512, 0 restores it).  Process-global; tests lower it so that

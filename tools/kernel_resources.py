@@ -54,7 +54,9 @@ def main():
     rows = collect()
     print('# Kernel resources of libdensereg_hip.so (hipcc -Rpass-analysis=kernel-resource-usage, gfx950)\n')
     print('Static, from the compiler: registers, scratch, LDS per workgroup and the occupancy they allow. Template arguments of')
-    print('`conv_igemm_kernel`: BM, BN, WM, WN, ABL (ablation, 0 = product), BK, GL (LDS-DMA refill), BF (bf16 operands).\n')
+    print('`conv_igemm_kernel`: BM, BN, WM, WN, ABL (ablation, 0 = product), BK, GL (LDS-DMA refill), BF (bf16 operands).')
+    print('`conv_bf16h_kernel` (the 3x3 halo kernel of the bf16 path): BN, log2 of the image width, waves, waves along the rows, XB (bit 0 a')
+    print('bf16-stored input, bit 1 the epilogue copies for bf16-stored outputs).\n')
     print('| kernel | VGPRs | AGPRs | SGPRs | scratch B/lane | LDS B/workgroup | waves/SIMD |')
     print('|---|---:|---:|---:|---:|---:|---:|')
     for n, r in rows:
