@@ -683,6 +683,8 @@ extern "C" int dr_dbg_force_bf16_halo(int on) {
     return DR_OK;
 }
 extern "C" long dr_dbg_bf16h_launches(void) { return g_bf16h_launches; }
+// conv_bf16hw.h (the same switch governs it; DR_BF16_HALOW=0 turns off that kernel alone): its launches of this process so far
+extern "C" long dr_dbg_bf16hw_launches(void) { return g_bf16hw_launches; }
 
 extern "C" int dr_dbg_force_bf16_storage(int on) {
     g_dbg_bf16_storage = on ? 1 : 0;

@@ -13,6 +13,7 @@
 #include "conv_x3h.h"
 #include "conv_x3hw.h"
 #include "conv_bf16h.h"
+#include "conv_bf16hw.h"
 #include "conv_wgrad.h"
 #include "conv_wgrad_bf16.h"
 #include "conv_wgrad_tr.h"
@@ -94,7 +95,8 @@ static bool conv_use_glds(const ConvParams& p) {
 static long g_x3h_launches = 0;      // conv_x3h.h launches of this process (dr_dbg_x3h_launches)
 static long g_x3hw_launches = 0;     // conv_x3hw.h launches of this process (dr_dbg_x3hw_launches)
 static long g_bf16h_launches = 0;    // conv_bf16h.h launches of this process (dr_dbg_bf16h_launches)
-static int g_dbg_bf16h = -1;         // test/bench hook (dr_dbg_force_bf16_halo): -1 = DR_BF16_HALO / the measured rule, 0 = never, 1 = wherever the kernel can run
+static long g_bf16hw_launches = 0;   // conv_bf16hw.h launches of this process (dr_dbg_bf16hw_launches)
+static int g_dbg_bf16h = -1;         // test/bench hook (dr_dbg_force_bf16_halo), conv_bf16h.h and conv_bf16hw.h: -1 = DR_BF16_HALO(W) / the measured rules, 0 = never, 1 = wherever each kernel can run
 static long g_p3_launches = 0;       // conv_p3.h launches of this process (test hook dr_dbg_p3_launches: "the kernel under test is the one that ran")
 static int g_force_tile = -1;        // test/bench hook (dr_dbg_conv_bench); -1 = heuristic
 static int g_dbg_bf16 = 0;           // test/bench hook (dr_dbg_force_bf16): dr_dbg_conv2d / dr_dbg_conv_bench run the bf16 kernels
@@ -297,6 +299,66 @@ static void launch_bf16h(const ConvParams& p, hipStream_t s) {
     ++g_bf16h_launches;
 }
 
+// conv_bf16hw.h: the same on 256-row blocks for the 64- and 128-pixel-wide maps (256x256 / 512x512 crops), in place of the same three 64-row
+// tiles of conv_igemm's BF kernel, bit for bit.  Needs 256-row blocks of whole image rows that lie in one micro-batch group.
+// DR_BF16_HALO=0 / dr_dbg_force_bf16_halo(0): never (with conv_bf16h.h); DR_BF16_HALOW=0: this kernel alone off; dr_dbg_force_bf16_halo(1):
+// wherever it can run; otherwise the measured rule bf16hw_wired.
+// Measured per launch against conv_igemm's BF kernel, alternating in one process (profiles/conv_bf16_halo_wide.md, section 1: the table this
+// rule is read from; workgroups = 256-row blocks x column blocks).  Wired where the kernel was faster beyond the spread between repeats:
+//   W = 64:  128 columns from 256 workgroups (1.14-1.69x), with an fp32-stored input from 128 (1.11x; bf16-stored 0.99x: not wired);
+//            64 columns from 256 (1.14-1.44x); 96 columns from 640, the smallest grid measured (1.25-1.41x).
+//   W = 128: 128 and 96 columns from 640 workgroups (1.07-1.45x and 1.21-1.36x); 128 columns on 128 / 320 workgroups -- half a round and 1.25
+//            rounds of one workgroup per CU -- measured 0.90-1.08x and stay on conv_igemm; 64 columns lost at every grid (0.91-0.99x): not wired.
+// The storage classes with bf16-stored outputs (XB bit 1: the epilogue only) have no per-launch entry and follow their input's class; they
+// run in the end-to-end training legs of section 2.
+static bool bf16hw_wired(int W, int bn, int xb, long workgroups) {
+    if (W == 64) return bn == 128 ? workgroups >= ((xb & 1) ? 256 : 128) : bn == 64 ? workgroups >= 256 : workgroups >= 640;
+    return bn != 64 && workgroups >= 640;
+}
+static bool conv_use_bf16hw(const ConvParams& p) {
+    static const bool env_on = [] {
+        const char* e = getenv("DR_BF16_HALO"); const char* w = getenv("DR_BF16_HALOW");
+        return !(e && e[0] == '0') && !(w && w[0] == '0');
+    }();
+    const int mode = g_dbg_bf16h >= 0 ? g_dbg_bf16h : (env_on ? -1 : 0);
+    if (mode == 0 || !p.bf16 || p.ksize != 3 || p.rowmask || (p.W != 64 && p.W != 128) || (p.H * p.W) % 256 != 0 || p.Kp % 32 != 0) return false;
+    if (p.grp_rows > 0 && p.grp_rows % 256 != 0) return false;
+    const int t = conv_tile_id(p), ncols = p.Ng > 0 ? p.Ng : p.Np;
+    if (t != KID_CONV_64x128 && t != KID_CONV_64x64 && !(t == KID_CONV_64x96 && ncols == 96)) return false;
+    if (mode == 1) return true;
+    const int bn = t == KID_CONV_64x128 ? 128 : t == KID_CONV_64x64 ? 64 : 96;
+    const int xb = (p.x_bf16 ? 1 : 0) | ((p.y_bf16 || p.bst_raw_bf16) ? 2 : 0);
+    return bf16hw_wired(p.W, bn, xb, (long)(p.B * p.H * p.W / 256) * dr_ceil_div(ncols, bn));
+}
+template <int BN, int W, int NW, int WM>
+static void launch_bf16hw_tile(const ConvParams& q, dim3 grid, hipStream_t s) {
+    switch ((q.x_bf16 ? 1 : 0) | ((q.y_bf16 || q.bst_raw_bf16) ? 2 : 0)) {
+        case 0: DR_LAUNCH((conv_bf16hw_kernel<BN, W, NW, WM, 0>), grid, dim3(NW * 64), 0, s, q); break;
+        case 1: DR_LAUNCH((conv_bf16hw_kernel<BN, W, NW, WM, 1>), grid, dim3(NW * 64), 0, s, q); break;
+        case 2: DR_LAUNCH((conv_bf16hw_kernel<BN, W, NW, WM, 2>), grid, dim3(NW * 64), 0, s, q); break;
+        default: DR_LAUNCH((conv_bf16hw_kernel<BN, W, NW, WM, 3>), grid, dim3(NW * 64), 0, s, q); break;
+    }
+}
+static void launch_bf16hw(const ConvParams& p, hipStream_t s) {
+    static const int nfast = [] { const char* e = getenv("DR_CONV_NFAST"); return (e && e[0] == '0') ? 0 : 1; }();
+    ConvParams q = p;
+    q.nfast = nfast;
+    const int t = conv_tile_id(p), ncols = p.Ng > 0 ? p.Ng : p.Np;
+    const int bn = t == KID_CONV_64x128 ? 128 : t == KID_CONV_64x64 ? 64 : 96;
+    const dim3 grid((unsigned)(p.B * p.H * p.W / 256), (unsigned)dr_ceil_div(ncols, bn));
+    q.gx = (int)grid.x; q.gy = (int)grid.y;
+    if (p.W == 64) {
+        if (bn == 128) launch_bf16hw_tile<128, 64, 16, 4>(q, grid, s);
+        else if (bn == 64) launch_bf16hw_tile<64, 64, 8, 4>(q, grid, s);
+        else launch_bf16hw_tile<96, 64, 8, 8>(q, grid, s);
+    } else {
+        if (bn == 128) launch_bf16hw_tile<128, 128, 16, 4>(q, grid, s);
+        else if (bn == 64) launch_bf16hw_tile<64, 128, 8, 4>(q, grid, s);
+        else launch_bf16hw_tile<96, 128, 8, 8>(q, grid, s);
+    }
+    ++g_bf16hw_launches;
+}
+
 // conv_p3.h (the x3 products on an input stored as its three bf16 planes): what the kernel can run -- whole 128-column blocks, at
 // least two K-tiles, the whole P3 tensor as input.  conv_p3_applies: the SHAPE rule alone, for the producer that must decide how
 // to store the tensor before the consumer's launch exists (train_exec.inc); conv_use_p3: + "the input is there".
@@ -470,6 +532,7 @@ int launch_conv_igemm(const ConvParams& p, hipStream_t s) {
     if (p.bf16) {
         if (p.Kp % 32) return -1;
         if (conv_use_bf16h(p)) { launch_bf16h(p, s); return 0; }
+        if (conv_use_bf16hw(p)) { launch_bf16hw(p, s); return 0; }
         switch (conv_tile_id(p)) {
             case KID_CONV_128x128: launch_cfg<128, 128, 2, 2, 16, 0, 1>(p, s); break;
             case KID_CONV_64x128: launch_cfg<64, 128, 2, 2, 16, 0, 1>(p, s); break;

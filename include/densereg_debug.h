@@ -137,6 +137,9 @@ long dr_dbg_x3hw_launches(void);
  * dr_dbg_bf16h_launches: its launches of this process so far. */
 int dr_dbg_force_bf16_halo(int on);
 long dr_dbg_bf16h_launches(void);
+/* dr_dbg_bf16hw_launches: conv_bf16hw_kernel launches (densereg_amd/csrc/conv_bf16hw.h: the same kernel on 256-row blocks for 64- and
+ * 128-pixel-wide images) of this process so far; dr_dbg_force_bf16_halo and DR_BF16_HALO=0 govern that kernel too, DR_BF16_HALOW=0 it alone. */
+long dr_dbg_bf16hw_launches(void);
 
 /* Partial statistics rows one wave of a BatchReNorm finalize launch folds before the micro-batch group gets another wave
  * (densereg_amd/csrc/train_kernels.h: bn_finalize_split; default 512, 0 restores it).  Process-global; tests lower it so that

@@ -56,7 +56,8 @@ def main():
     print('Static, from the compiler: registers, scratch, LDS per workgroup and the occupancy they allow. Template arguments of')
     print('`conv_igemm_kernel`: BM, BN, WM, WN, ABL (ablation, 0 = product), BK, GL (LDS-DMA refill), BF (bf16 operands).')
     print('`conv_bf16h_kernel` (the 3x3 halo kernel of the bf16 path): BN, log2 of the image width, waves, waves along the rows, XB (bit 0 a')
-    print('bf16-stored input, bit 1 the epilogue copies for bf16-stored outputs).\n')
+    print('bf16-stored input, bit 1 the epilogue copies for bf16-stored outputs).  `conv_bf16hw_kernel` (the same on 256-row blocks): BN, the')
+    print('image width (64 / 128), waves, waves along the rows, XB.\n')
     print('| kernel | VGPRs | AGPRs | SGPRs | scratch B/lane | LDS B/workgroup | waves/SIMD |')
     print('|---|---:|---:|---:|---:|---:|---:|')
     for n, r in rows:

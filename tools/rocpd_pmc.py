@@ -48,7 +48,7 @@ def short_name(n):
         return 'conv_igemm_%sx%s' % (m.group(1), m.group(2))
     if 'conv_x3_kernel' in n or 'conv_x3h_kernel' in n or 'conv_x3hw_kernel' in n:            # every tile / variant of conv_x3.h and conv_x3h.h is one profile row (net.h: KID_CONV_X3)
         return 'conv_x3_128x128'
-    m = re.search(r'conv_bf16h_kernel<(\d+)', n)                   # accounted under the 64-row conv_igemm tile it replaces (conv_bf16h.h)
+    m = re.search(r'conv_bf16hw?_kernel<(\d+)', n)                 # accounted under the 64-row conv_igemm tile it replaces (conv_bf16h.h, conv_bf16hw.h)
     if m:
         return 'conv_igemm_64x%s' % m.group(1)
     if 'conv_splitk_kernel' in n:
